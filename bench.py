@@ -17,6 +17,14 @@ launches if it fails anywhere).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
                     [--model resnet50|resnet152|vit_b_16] [--backend native|torch]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line. ``--full`` adds
+what the headline figure does not need: the gradient all-reduce probe (N > 1), the check
+that all ranks hold the same weights, and the idle-GPU host enqueue time of one more step.
+``--dump-outputs DIR`` writes the last timed step's loss, logits and (a fixed sample of) the
+updated parameters to ``DIR/*.npy``; model, data and sample are seeded, so two builds run
+with the same arguments can be compared output for output.
 
 N > 1: either launch it under ``torch.distributed.run`` (one rank per GPU,
 ``--gpus`` must equal WORLD_SIZE), or run ``python bench.py --gpus N`` directly:
@@ -168,6 +176,13 @@ def parse():
     ap.add_argument("--eager", dest="graph", action="store_false",
                     help="launch the step's kernels one by one (the default)")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the gradient all-reduce probe (N > 1), "
+                         "the rank-consistency check of the weights and the idle-GPU host enqueue time of one "
+                         "more step (a plain run sets up, warms up, times the steps and prints the result)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed to DIR/<name>.npy "
+                         "(float32): loss, logits and a fixed seeded sample of the updated parameters")
     ap.add_argument("--miopen-find", type=int, default=1, choices=[0, 1],
                     help="torch backend: 1 = cudnn.benchmark (MIOpen find), 0 = immediate mode")
     ap.add_argument("--dist-backend", default=None, choices=[None, "nccl", "gloo"],
@@ -186,6 +201,8 @@ def parse():
                     help="cpu: gloo ranks on the host with stock torch ops (launcher/plumbing rehearsal)")
     ap.add_argument("--image-size", type=int, default=224, help="only for --device cpu rehearsals")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.batch is None:
         a.batch = DEFAULT_BATCH.get(a.model, 256)
     if a.graph is None:
@@ -361,6 +378,39 @@ def rank_consistency(model, device, world):
             "param_checksum_max_rank_diff": diff, "ranks_checked": world}
 
 
+# --dump-outputs: elements kept of the logits / of the parameters (float32: 32 MB + 16 MB)
+DUMP_MAX_LOGITS = 8 * 2 ** 20
+DUMP_MAX_PARAMS = 4 * 2 ** 20
+
+
+def _dump_sample(flat: torch.Tensor, limit: int, seed: int) -> torch.Tensor:
+    """``flat`` as float32 on the host; above ``limit`` elements a fixed sample of it (sorted
+    indices from a seeded host generator: the same elements in every run and every build)."""
+    if flat.numel() > limit:
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randint(0, flat.numel(), (limit,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu()
+
+
+@torch.no_grad()
+def dump_outputs(path, loss, logits, model):
+    """What the last timed step handed back, as ``path/<name>.npy`` (float32): its loss, its
+    logits ([per-GPU batch, classes]) and the parameters it left behind (in
+    ``model.parameters()`` order, flattened; a fixed sample of them above DUMP_MAX_PARAMS)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().reshape(1).numpy())
+    lg = logits.detach()
+    if lg.numel() > DUMP_MAX_LOGITS:
+        lg = _dump_sample(lg.reshape(-1), DUMP_MAX_LOGITS, 20240)
+    else:
+        lg = lg.float().cpu()
+    np.save(os.path.join(path, "logits.npy"), lg.numpy())
+    flat = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+    np.save(os.path.join(path, "params.npy"), _dump_sample(flat, DUMP_MAX_PARAMS, 20241).numpy())
+
+
 def any_rank(flag: bool, device) -> bool:
     """True on every rank if ``flag`` is True on any rank (so all ranks take the same exit)."""
     if not pdist_ready():
@@ -491,7 +541,7 @@ def main():
 
     # N ranks: rank 0 tunes the kernel variants once and broadcasts them (no per-rank timing)
     pretune_for_ddp(model, _pretune_step)
-    ar = allreduce_probe(model, device, world)
+    ar = allreduce_probe(model, device, world) if args.full else None
     graph_fallback = None
     graph_check, bad = None, False
     if args.graph and not args.no_ddp:
@@ -510,12 +560,16 @@ def main():
         model = wrap_ddp(model, device, bucket_cap_mb=args.bucket_mb, broadcast_buffers=False,
                          gradient_as_bucket_view=True, comm_hook=args.comm_hook, impl=args.ddp_impl)
 
+    last = {}  # --dump-outputs: the logits of the latest step
+
     def step(i):
         x, y = next_batch(i)
         opt.zero_grad(set_to_none=True)
         with torch.autocast(dev_type, dtype=torch.bfloat16, enabled=autocast):
             out = model(x)
             loss = fused.softmax_cross_entropy(out, y)
+        if args.dump_outputs:
+            last["logits"] = out.detach()
         loss.backward()
         opt.step()
         return loss
@@ -540,6 +594,8 @@ def main():
             with torch.autocast(dev_type, dtype=torch.bfloat16, enabled=autocast):
                 out = model(sx)
                 loss = fused.softmax_cross_entropy(out, sy)
+            if args.dump_outputs:
+                last["logits"] = out.detach()  # in the capture: the static buffer every replay writes
             loss.backward()
             opt.step()
             return loss
@@ -701,20 +757,22 @@ def main():
     if any_rank(not (math.isfinite(loss_first) and math.isfinite(loss_last)), device):
         refuse(rank, record(None, ms, losses), f"non-finite training loss (first {loss_first}, last {loss_last})",
                args.json_out)
-    sync_rec = rank_consistency(model, device, world)
-    if not sync_rec["ranks_in_sync"] and rank == 0:
-        print(f"bench.py: WARNING ranks diverged after the timed steps: {sync_rec}", file=sys.stderr, flush=True)
-    losses.update(sync_rec)
-    # host enqueue cost of one step with an idle GPU (cpu_issue above includes the time the
-    # host waits on a full submission queue while the GPU is busy)
-    sync()
-    h0 = time.perf_counter()
-    step(args.steps)
-    host_enqueue_ms = (time.perf_counter() - h0) * 1e3
-    sync()
-
-    losses.update({"cpu_issue_ms_per_step": round(cpu_issue / args.steps * 1e3, 3),
-                   "host_enqueue_ms_idle_gpu": round(host_enqueue_ms, 3)})
+    if args.dump_outputs and rank == 0:  # before --full steps once more
+        dump_outputs(args.dump_outputs, loss, last["logits"], model)
+    losses["cpu_issue_ms_per_step"] = round(cpu_issue / args.steps * 1e3, 3)
+    if args.full:
+        sync_rec = rank_consistency(model, device, world)
+        if not sync_rec["ranks_in_sync"] and rank == 0:
+            print(f"bench.py: WARNING ranks diverged after the timed steps: {sync_rec}", file=sys.stderr, flush=True)
+        losses.update(sync_rec)
+        # host enqueue cost of one step with an idle GPU (cpu_issue above includes the time the
+        # host waits on a full submission queue while the GPU is busy)
+        sync()
+        h0 = time.perf_counter()
+        step(args.steps)
+        host_enqueue_ms = (time.perf_counter() - h0) * 1e3
+        sync()
+        losses["host_enqueue_ms_idle_gpu"] = round(host_enqueue_ms, 3)
     rec = record(value, ms, losses)
     if rank == 0:
         line = json.dumps(rec)

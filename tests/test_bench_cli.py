@@ -33,8 +33,8 @@ def _json_line(out: str) -> dict:
 
 def test_bench_self_launches_two_cpu_ranks():
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--device", "cpu", "--batch", "2", "--image-size", "32",
-                        "--steps", "1", "--warmup", "1"], cwd=ROOT, env=_env(), capture_output=True, text=True,
-                       timeout=600)
+                        "--steps", "1", "--warmup", "1", "--full"], cwd=ROOT, env=_env(), capture_output=True,
+                       text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _json_line(r.stdout)
     assert rec["n_gpus"] == 2
@@ -80,12 +80,42 @@ def test_bench_one_rank_runs_ddp_over_a_process_group():
     assert rec["config"]["ddp"] is False and rec["config"]["dist_backend"].startswith("none")
 
 
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run carries the headline fields but none of the ``--full`` extras, and
+    ``--dump-outputs`` writes the last timed step's loss / logits / parameters as float32
+    ``.npy`` files that a second run with the same arguments reproduces."""
+    import numpy as np
+    dumps = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--device", "cpu", "--batch", "2", "--image-size",
+                            "32", "--steps", "2", "--warmup", "1", "--no-ddp", "--dump-outputs", str(d)], cwd=ROOT,
+                           env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = _json_line(r.stdout)
+        dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert rec[k] is not None, k
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+    assert abs(rec["value"] - 2 / (rec["ms_per_step"] / 1e3)) <= 0.01 * rec["value"]
+    for k in ("ranks_in_sync", "host_enqueue_ms_idle_gpu"):
+        assert k not in rec["config"], k
+    a, b = dumps
+    assert sorted(a) == ["logits.npy", "loss.npy", "params.npy"] == sorted(b)
+    assert a["logits.npy"].shape == (2, 1000) and a["loss.npy"].shape == (1,)
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=1e-6, err_msg=k)
+    assert abs(float(a["loss.npy"][0]) - rec["config"]["loss_last"]) < 1e-3
+
+
 def test_bench_eight_cpu_ranks_one_json_line():
     """The driver's N = 8 launch, rehearsed on 8 gloo ranks: one JSON line from rank 0 with
     the whole-job numbers (dp8), finite first / last losses."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--device", "cpu", "--batch", "2", "--image-size", "32",
-                        "--steps", "2", "--warmup", "1"], cwd=ROOT, env=_env(), capture_output=True, text=True,
-                       timeout=900)
+                        "--steps", "2", "--warmup", "1", "--full"], cwd=ROOT, env=_env(), capture_output=True,
+                       text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _json_line(r.stdout)
     assert rec["n_gpus"] == 8 and rec["config"]["parallelism"] == "dp8"

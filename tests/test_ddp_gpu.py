@@ -83,8 +83,8 @@ def test_bench_two_gloo_ranks_native_kernels_reducer_in_sync():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-                        "--batch", "64", "--steps", "3", "--warmup", "1"], cwd=root, env=env, capture_output=True,
-                       text=True, timeout=600)
+                        "--batch", "64", "--steps", "3", "--warmup", "1", "--full"], cwd=root, env=env,
+                       capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
     assert len(lines) == 1, r.stdout[-2000:]
