@@ -108,6 +108,13 @@ _SIGS = {
     "pdt_sgd_step2": (c_int, [P, c_int, P, P, P, P, c_float, c_float, c_float, c_float, c_int, c_int, c_float, P, P]),
     "pdt_adam_step2": (c_int, [P, c_int, P, P, P, P, P, P] + [c_float] * 5 + [c_int, c_float, c_float, c_float, P,
                                                                             c_int, P]),
+    "pdt_sumsq_chunks": (c_int, [P, c_int, P, P, P, P]),
+    "pdt_norm_finalize": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, c_float, P]),
+    "pdt_lars_step": (c_int, [P, c_int, P, P, P, P, P, P, c_int, P, c_float, c_float, c_float, c_int, c_float,
+                              c_float, P, P]),
+    "pdt_lamb_tick": (c_int, [P, c_double, c_double, P]),
+    "pdt_lamb_stage1": (c_int, [P, c_int, P, P, P, P, P, P, P] + [c_float] * 8 + [P, P]),
+    "pdt_lamb_stage2": (c_int, [P, c_int, P, P, P, P, P, P, c_int] + [c_float] * 5 + [P, P]),
     "pdt_fill_uniform_bf16": (c_int, [P, c_long, c_uint, P]),
     "pdt_cast_f32_bf16": (c_int, [P, P, c_long, P]),
     "pdt_synth_images_bf16": (c_int, [P, P, c_long, c_int, c_int, c_int, c_uint, P, c_int, P]),
@@ -247,6 +254,16 @@ def _p(t):
 def _chk(rc, name):
     if rc != 0:
         raise RuntimeError(f"{name} failed with code {rc}")
+
+
+def multi_tensor_l2norm(tensors):
+    """``(per_tensor_norms, global_norm)`` of fp32 CUDA tensors (contiguous or channels_last-dense):
+    a float32 device tensor of ``len(tensors)`` and a 0-d device tensor, from two launches whatever
+    the number of tensors, with fixed-order sums (bitwise repeatable) and no host sync -- e.g. to
+    log a gradient norm. The kernels are the ones FusedLARS / FusedLAMB step with
+    (``csrc/optim_layerwise.hip``); the work list is built by ``optim/fused.py``."""
+    from ..optim.fused import multi_tensor_l2norm as impl
+    return impl(tensors)
 
 
 def _grad_buf(param, shape, memory_format=None, device=None):

@@ -1,2 +1,2 @@
 """Optimizers. ``optimizer.type`` in config resolves here first, then in torch.optim."""
-from .fused import FusedSGD, FusedAdam, FusedAdamW  # noqa: F401
+from .fused import FusedSGD, FusedAdam, FusedAdamW, FusedLARS, FusedLAMB  # noqa: F401

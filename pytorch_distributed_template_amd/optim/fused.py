@@ -26,6 +26,11 @@ a group to receive a gradient on every step (a captured graph assumes that anywa
 ``step()`` raises if the set of parameters with gradients changes between steps --
 torch's per-parameter counts would diverge from the group count there, and a checkpoint
 reloaded into torch.optim would apply different bias corrections.
+
+``FusedLARS`` / ``FusedLAMB`` (second half of this file, ``csrc/optim_layerwise.hip``) are the
+layer-wise optimizers of the large-batch recipes, with global gradient-norm clipping on the
+device; they are built on ``multi_tensor_l2norm``, a deterministic per-tensor L2 norm whose
+results stay in device memory.
 """
 from __future__ import annotations
 
@@ -407,3 +412,403 @@ class FusedAdamW(FusedAdam):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False,
                  write_bf16_shadow=True, capturable=False):
         super().__init__(params, lr, betas, eps, weight_decay, amsgrad, write_bf16_shadow, capturable)
+
+
+# =============================================================================
+# Layer-wise adaptive optimizers (LARS, LAMB) with on-device gradient-norm clipping
+# (csrc/optim_layerwise.hip)
+# =============================================================================
+class _NormTables:
+    """What the norm kernels need next to a ``_Plan``: ``chunk_begin[n + 1]`` (a tensor's
+    chunks are consecutive in the chunk table), ``flags[n]`` (bit 0: layer-wise adaptation and
+    weight decay apply), the per-chunk partial sums and the per-tensor norms ``[2, n]``."""
+
+    def __init__(self, plan, params, adapt):
+        import numpy as np
+        n = len(params)
+        begin = np.zeros(n + 1, dtype=np.int32)
+        begin[1:] = np.cumsum([(p.numel() + CHUNK - 1) // CHUNK for p in params])
+        assert int(begin[-1]) == plan.nchunks, (int(begin[-1]), plan.nchunks)
+        dev = plan.device
+        self.key = tuple(adapt)
+        self.n = n
+        self.chunk_begin = _to_device_async(torch.from_numpy(begin), dev)
+        self.flags = _to_device_async(torch.tensor([int(a) for a in adapt], dtype=torch.int32), dev)
+        self.partials = torch.zeros(2 * max(plan.nchunks, 1), dtype=torch.float32, device=dev)
+        self.norms = torch.zeros((2, max(n, 1)), dtype=torch.float32, device=dev)
+
+
+def _norm_tables(plan, params, adapt):
+    nt = getattr(plan, "norm_tables", None)
+    if nt is None or nt.key != tuple(adapt):
+        nt = plan.norm_tables = _NormTables(plan, params, adapt)
+    return nt
+
+
+def _dense_grads(params):
+    """fp32 gradients laid out like their parameters (what the kernels index)."""
+    grads = [p.grad if p.grad.dtype == torch.float32 else p.grad.float() for p in params]
+    return [g if g.stride() == p.stride() else g.contiguous(memory_format=torch.channels_last
+                                                             if p.dim() == 4 else torch.contiguous_format)
+            for g, p in zip(grads, params)]
+
+
+def multi_tensor_l2norm(tensors):
+    """Per-tensor L2 norms (float32 device tensor of ``len(tensors)``) and their global L2 norm
+    (0-d device tensor) of fp32 CUDA tensors, contiguous or channels_last-dense: two launches
+    for any number of tensors, deterministic (fixed-order sums, no atomics), no host sync."""
+    from ..ops import native_ops
+    tensors = list(tensors)
+    if not tensors:
+        raise ValueError("multi_tensor_l2norm: no tensors")
+    dev = tensors[0].device
+    for t in tensors:
+        if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and (
+                t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)))):
+            raise ValueError("multi_tensor_l2norm: fp32 CUDA tensors on one device, contiguous or "
+                             f"channels_last-dense (got {tuple(t.shape)} {t.dtype} {t.device} strides {t.stride()})")
+    lib = native_ops._load()
+    plan = _Plan(tensors, dev)
+    plan.update({"a": tensors})
+    nt = _norm_tables(plan, tensors, [0] * len(tensors))
+    glob = torch.zeros(4, dtype=torch.float32, device=dev)
+    st = torch.cuda.current_stream().cuda_stream
+    native_ops._chk(lib.pdt_sumsq_chunks(plan.chunks.data_ptr(), plan.nchunks, plan.ptr("a"), None,
+                                         nt.partials.data_ptr(), st), "sumsq_chunks")
+    native_ops._chk(lib.pdt_norm_finalize(nt.partials.data_ptr(), nt.chunk_begin.data_ptr(), nt.n, 1, 0,
+                                          nt.norms.data_ptr(), glob.data_ptr(), 1, 0.0, st), "norm_finalize")
+    return nt.norms[0, :nt.n], glob[2]
+
+
+class _LayerwiseBase(_FusedBase):
+    """Shared by FusedLARS / FusedLAMB: the adapt flags, the global gradient norm and clip
+    coefficient (one device buffer for the optimizer, combined over the param groups in group
+    order), the norm launches.
+
+    The global norm spans every group, so the native path runs only when every group with
+    gradients passes ``_native_ok``; otherwise the whole step runs ``_torch_step``."""
+
+    def __init__(self, params, defaults, max_grad_norm, write_bf16_shadow, capturable):
+        super().__init__(params, defaults, write_bf16_shadow, capturable)
+        self.max_grad_norm = float(max_grad_norm)
+        self._glob = None  # device [sum of squares (one double), gnorm, clip]
+
+    def load_state_dict(self, state_dict):
+        """torch's; a checkpoint written by ``torch.optim.SGD`` / ``Adam`` has none of the
+        layer-wise hyperparameters, so groups take the ones this optimizer was built with."""
+        super().load_state_dict(state_dict)
+        for group in self.param_groups:
+            for k, v in self.defaults.items():
+                group.setdefault(k, v)
+
+    def _step_prologue(self):
+        if torch.cuda.is_available():  # (capturable is harmless on a machine without a GPU)
+            super()._step_prologue()
+
+    @staticmethod
+    def _adapt(group, p):
+        return not (group["exclude_1d"] and p.dim() <= 1)
+
+    def _work(self):
+        work = []
+        for gi, group in enumerate(self.param_groups):
+            params = [p for p in group["params"] if p.grad is not None]
+            if params:
+                work.append((gi, group, params))
+        return work
+
+    def _global(self, device):
+        if self._glob is None or self._glob.device != device:
+            self._glob = torch.zeros(4, dtype=torch.float32, device=device)
+            self._glob[3] = 1.0
+        return self._glob
+
+    def _tables(self, gi, group, params, roles):
+        plan = self._plan(gi, params, roles, params[0].device)
+        return plan, _norm_tables(plan, params, [self._adapt(group, p) for p in params])
+
+    def _sumsq(self, plan, nt, a, b):
+        from ..ops import native_ops
+        native_ops._chk(native_ops._load().pdt_sumsq_chunks(
+            plan.chunks.data_ptr(), plan.nchunks, plan.ptr(a), plan.ptr(b) if b else None,
+            nt.partials.data_ptr(), self._stream()), "sumsq_chunks")
+
+    def _finalize(self, nt, nroles, grole, glob, start_zero):
+        from ..ops import native_ops
+        native_ops._chk(native_ops._load().pdt_norm_finalize(
+            nt.partials.data_ptr(), nt.chunk_begin.data_ptr(), nt.n, nroles, grole, nt.norms.data_ptr(),
+            glob.data_ptr() if glob is not None else None, int(start_zero), self.max_grad_norm,
+            self._stream()), "norm_finalize")
+
+    def _finish(self, params, shadows):
+        from ..ops import native_ops
+        _bump_versions(params)
+        if self.write_bf16_shadow:
+            for p, s in zip(params, shadows):
+                native_ops.register_shadow(p, s)
+
+    def _torch_clip(self, work):
+        """The clip coefficient as a 0-d fp32 tensor (no host sync), or None without clipping."""
+        if self.max_grad_norm <= 0:
+            return None
+        sq = [p.grad.double().pow(2).sum() for _, _, params in work for p in params]
+        gnorm = torch.stack([s.to(sq[0].device) for s in sq]).sum().sqrt()
+        return torch.clamp(self.max_grad_norm / (gnorm + 1e-6), max=1.0).float()
+
+    def grad_norm(self):
+        """The global gradient norm of the last native step as a 0-d device tensor (before
+        clipping; no host sync), or None if no native step has run."""
+        return None if self._glob is None else self._glob[2]
+
+
+class FusedLARS(_LayerwiseBase):
+    """LARS (You et al. 2017): SGD-momentum with a layer-wise trust ratio, for large-batch
+    ResNet training. With ``g' = clip g``, ``wn = |w|``, ``gn = clip |g|`` per tensor::
+
+        adapted:   q = trust_coefficient wn / (gn + wd wn + eps)  (1 if wn or gn is 0)
+                   d = q (g' + wd w)
+        excluded:  d = g'                       (no weight decay, no trust ratio)
+        buf = momentum buf + d   (buf = d on a tensor's first step)
+        d = d + momentum buf if nesterov else buf
+        w -= lr d
+
+    ``exclude_1d`` excludes parameters with ``dim() <= 1`` (biases, BatchNorm / LayerNorm
+    affine). ``max_grad_norm > 0`` clips the global gradient norm (every param group's
+    gradients; ``clip = min(1, max_grad_norm / (gnorm + 1e-6))``) on the device: under DDP it
+    is computed from the averaged gradients, identical on every rank, with no collective.
+
+    Three launches per param group (sum of squares of w and g, finalize, step), none of them
+    blocking the host. The state is ``momentum_buffer``: a checkpoint loads into
+    ``torch.optim.SGD`` once the extra hyperparameters are dropped, and back.
+
+    ``capturable=True``: the lr is read from device memory (``refresh_scalars()``). Momentum
+    buffers are created, zeroed, by the first eager step; a captured step that would have to
+    create one raises (the graph would zero the buffer again on every replay) -- capture after
+    an eager warm-up step."""
+
+    def __init__(self, params, lr, momentum=0.9, weight_decay=0.0, nesterov=False, trust_coefficient=1e-3,
+                 eps=1e-8, exclude_1d=True, max_grad_norm=0.0, write_bf16_shadow=True, capturable=False):
+        defaults = dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov,
+                        trust_coefficient=trust_coefficient, eps=eps, exclude_1d=exclude_1d)
+        super().__init__(params, defaults, max_grad_norm, write_bf16_shadow, capturable)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._step_prologue()
+        work = self._work()
+        if not work:
+            return loss
+        if not all(_native_ok(params) for _, _, params in work):
+            self._torch_step(work)
+            return loss
+        from ..ops import native_ops
+        lib = native_ops._load()
+        capturing = torch.cuda.is_current_stream_capturing()
+        for _, group, params in work:
+            if group["momentum"] == 0:
+                continue
+            for p in params:
+                st = self.state[p]
+                if st.get("momentum_buffer") is None:
+                    if capturing:
+                        raise RuntimeError(
+                            "FusedLARS: this step would create a momentum buffer, which cannot happen inside "
+                            "a graph capture (its zero fill would replay); run an eager step first")
+                    st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        glob = self._global(work[0][2][0].device)
+        launches = []
+        for k, (gi, group, params) in enumerate(work):
+            mom = group["momentum"] != 0
+            none = [None] * len(params)
+            shadows = [self._shadow(p) for p in params]
+            roles = {"p": params, "g": _dense_grads(params),
+                     "b": [self.state[p]["momentum_buffer"] for p in params] if mom else none,
+                     "s": shadows if self.write_bf16_shadow else none}
+            plan, nt = self._tables(gi, group, params, roles)
+            self._sumsq(plan, nt, "p", "g")
+            self._finalize(nt, 2, 1, glob, k == 0)
+            launches.append((gi, group, params, shadows, plan, nt, mom))
+        # every group's finalize has run: glob holds the norm over all of them
+        for gi, group, params, shadows, plan, nt, mom in launches:
+            dev = self._dev_scalars(gi, group, params[0].device) if self.capturable else None
+            rc = lib.pdt_lars_step(
+                plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("g"),
+                plan.ptr("b") if mom else None, plan.ptr("s") if self.write_bf16_shadow else None,
+                nt.flags.data_ptr(), nt.norms.data_ptr(), nt.n, glob.data_ptr(), float(group["lr"]),
+                float(group["momentum"]), float(group["weight_decay"]), int(group["nesterov"]),
+                float(group["trust_coefficient"]), float(group["eps"]),
+                dev.data_ptr() if dev is not None else None, self._stream())
+            native_ops._chk(rc, "lars_step")
+            self._finish(params, shadows)
+        return loss
+
+    def _torch_step(self, work):
+        clip = self._torch_clip(work)
+        for _, group, params in work:
+            wd, mom = group["weight_decay"], group["momentum"]
+            for p in params:
+                g = p.grad if clip is None else p.grad * clip.to(p.device)
+                if self._adapt(group, p):
+                    wn, gn = p.double().norm(), g.double().norm()
+                    q = torch.where((wn > 0) & (gn > 0),
+                                    group["trust_coefficient"] * wn / (gn + wd * wn + group["eps"]),
+                                    torch.ones_like(wn)).to(p.dtype)
+                    d = g.add(p, alpha=wd).mul_(q)
+                else:
+                    d = g
+                if mom != 0:
+                    st = self.state[p]
+                    buf = st.get("momentum_buffer")
+                    if buf is None:
+                        buf = st["momentum_buffer"] = torch.clone(d).detach()
+                    else:
+                        buf.mul_(mom).add_(d)
+                    d = d.add(buf, alpha=mom) if group["nesterov"] else buf
+                p.add_(d, alpha=-group["lr"])
+
+
+class FusedLAMB(_LayerwiseBase):
+    """LAMB (You et al. 2020): Adam moments with a layer-wise trust ratio, for large-batch
+    transformer training. With ``g' = clip g``::
+
+        m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2
+        u = (m / bc1) / (sqrt(v / bc2) + eps) + wd w          (wd = 0 on excluded tensors)
+        r = |w| / |u| on adapted tensors with |w| > 0 and |u| > 0, else 1
+        w -= lr r u
+
+    ``exclude_1d`` and ``max_grad_norm`` as in ``FusedLARS``. Per param group: stage 1 (moments
+    and the partial sums of |u|^2, |w|^2), finalize, stage 2 (u recomputed from the moments: no
+    scratch tensor) -- 3 launches, 5 with clipping (a sum-of-squares pass over g and its
+    finalize first). The state is ``step`` / ``exp_avg`` / ``exp_avg_sq``: a checkpoint loads
+    into ``torch.optim.Adam`` once the extra hyperparameters are dropped, and back.
+
+    ``capturable=True`` as in ``FusedAdam``: lr and the step count live in device memory, the
+    count (and the bias corrections for it) advance on the device ahead of stage 1,
+    ``state_dict()`` writes the count back into ``step``, and the set of parameters with
+    gradients must not change between steps."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, exclude_1d=True,
+                 max_grad_norm=0.0, write_bf16_shadow=True, capturable=False):
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, exclude_1d=exclude_1d)
+        super().__init__(params, defaults, max_grad_norm, write_bf16_shadow, capturable)
+
+    def state_dict(self):
+        """torch's format; in capturable mode each parameter's ``step`` is first set from the
+        group's device step count (replayed graphs advance only that), as ``FusedAdam`` does."""
+        if self.capturable:
+            for gi, group in enumerate(self.param_groups):
+                d = self._dev.get(gi)
+                if d is None:
+                    continue
+                t = float(d[1].item())
+                for p in group["params"]:
+                    if p in self.state and "step" in self.state[p]:
+                        self.state[p]["step"] = torch.tensor(t)
+        return super().state_dict()
+
+    def _dev_scalars(self, gi, group, device, t0=0.0):
+        """The group's device [lr, t, bc1, bc2] (bc1 / bc2 are written by the tick kernel)."""
+        d = self._dev.get(gi)
+        if d is None:
+            d = torch.tensor([float(group["lr"]), float(t0), 1.0, 1.0], dtype=torch.float32, device=device)
+            self._dev[gi] = d
+            self._dev_lr[gi] = float(group["lr"])
+        return d
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._step_prologue()
+        work = self._work()
+        if not work:
+            return loss
+        native = all(_native_ok(params) for _, _, params in work)
+        dev_step = self.capturable and native
+        bcs = {}
+        for gi, group, params in work:
+            if dev_step:
+                key = tuple(id(p) for p in params)
+                seen = self._grad_sets.setdefault(gi, key)
+                if seen != key:
+                    raise RuntimeError(
+                        "capturable FusedLAMB: the set of parameters with gradients changed between steps "
+                        f"(group {gi}: {len(seen)} -> {len(key)} params); the group's single device step "
+                        "count requires every parameter to receive a gradient on every step")
+            for p in params:
+                st = self.state[p]
+                if len(st) == 0:
+                    st["step"] = torch.tensor(0.0)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                if not dev_step:  # (capturable: the device count is the step, see state_dict)
+                    st["step"] += 1
+            b1, b2 = group["betas"]
+            step = float(self.state[params[0]]["step"]) if not dev_step else 1.0
+            bcs[gi] = (1 - b1 ** step, 1 - b2 ** step)
+        if not native:
+            self._torch_step(work, bcs)
+            return loss
+        from ..ops import native_ops
+        lib = native_ops._load()
+        clipping = self.max_grad_norm > 0
+        glob = self._global(work[0][2][0].device) if clipping else None
+        launches = []
+        for k, (gi, group, params) in enumerate(work):
+            none = [None] * len(params)
+            shadows = [self._shadow(p) for p in params]
+            roles = {"p": params, "g": _dense_grads(params), "m": [self.state[p]["exp_avg"] for p in params],
+                     "v": [self.state[p]["exp_avg_sq"] for p in params],
+                     "s": shadows if self.write_bf16_shadow else none}
+            plan, nt = self._tables(gi, group, params, roles)
+            if clipping:
+                self._sumsq(plan, nt, "g", None)
+                self._finalize(nt, 1, 0, glob, k == 0)
+            launches.append((gi, group, params, shadows, plan, nt))
+        for gi, group, params, shadows, plan, nt in launches:
+            b1, b2 = group["betas"]
+            bc1, bc2 = bcs[gi]
+            dev = self._dev_scalars(gi, group, params[0].device, t0=float(self.state[params[0]]["step"])) \
+                if dev_step else None
+            devp = dev.data_ptr() if dev is not None else None
+            st = self._stream()
+            if dev is not None:
+                native_ops._chk(lib.pdt_lamb_tick(devp, float(b1), float(b2), st), "lamb_tick")
+            rc = lib.pdt_lamb_stage1(
+                plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("g"), plan.ptr("m"), plan.ptr("v"),
+                nt.flags.data_ptr(), nt.partials.data_ptr(), glob.data_ptr() if glob is not None else None,
+                float(b1), float(b2), float(1 - b1), float(1 - b2), float(group["eps"]), float(group["weight_decay"]),
+                float(bc1), float(bc2), devp, st)
+            native_ops._chk(rc, "lamb_stage1")
+            self._finalize(nt, 2, -1, None, False)
+            rc = lib.pdt_lamb_stage2(
+                plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("m"), plan.ptr("v"),
+                plan.ptr("s") if self.write_bf16_shadow else None, nt.flags.data_ptr(), nt.norms.data_ptr(), nt.n,
+                float(group["lr"]), float(group["eps"]), float(group["weight_decay"]), float(bc1), float(bc2),
+                devp, st)
+            native_ops._chk(rc, "lamb_stage2")
+            self._finish(params, shadows)
+        return loss
+
+    def _torch_step(self, work, bcs):
+        clip = self._torch_clip(work)
+        for gi, group, params in work:
+            b1, b2 = group["betas"]
+            bc1, bc2 = bcs[gi]
+            for p in params:
+                st = self.state[p]
+                g = p.grad if clip is None else p.grad * clip.to(p.device)
+                st["exp_avg"].mul_(b1).add_(g, alpha=1 - b1)
+                st["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1 - b2)
+                u = (st["exp_avg"] / bc1).div_((st["exp_avg_sq"] / bc2).sqrt_().add_(group["eps"]))
+                if self._adapt(group, p):
+                    u.add_(p, alpha=group["weight_decay"])
+                    wn, un = p.double().norm(), u.double().norm()
+                    u.mul_(torch.where((wn > 0) & (un > 0), wn / un, torch.ones_like(wn)).to(p.dtype))
+                p.add_(u, alpha=-group["lr"])

@@ -57,6 +57,10 @@ _FUSED_FOR = {
 }
 
 
+# the layer-wise optimizers have no torch.optim name: configs name them directly
+_LAYERWISE = ("FusedLARS", "FusedLAMB")
+
+
 def build_optimizer(config, model):
     """``optimizer.type`` is looked up in ``optim`` first, then ``torch.optim``. On the
     native GPU path a torch.optim SGD / Adam / AdamW (e.g. the reference's ``"Adam"``)
@@ -76,6 +80,9 @@ def build_optimizer(config, model):
         if config["trainer"].get("hip_graph", False) and str(ocfg["type"]).startswith("Fused") \
                 and "capturable" not in ocfg.get("args", {}):
             extra["capturable"] = True  # (optim.Fused*: lr / step counts in device memory)
+        if ocfg["type"] in _LAYERWISE and "write_bf16_shadow" not in ocfg.get("args", {}):
+            # fp32-only models (LeNet) read no bf16 weight shadow
+            extra["write_bf16_shadow"] = config["trainer"].get("precision") == "bf16"
         optimizer = config.init_obj("optimizer", [module_optim, torch.optim], params, **extra)
     lr_scheduler = None
     if config.get("lr_scheduler"):
