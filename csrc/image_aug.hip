@@ -1,0 +1,142 @@
+// Input pipeline on the device (data/packed.py PackedImageLoader): one launch turns a batch
+// of stored uint8 RGB images into the augmented, normalized bf16 batch in the zero-padded
+// 4-channel NHWC storage the space-to-depth stem reads in place.
+//
+// Per output pixel (oy, ox) of image b, with box = (y0, x0, h, w, flip):
+//   ox' = flip ? S-1-ox : ox
+//   sy = max((oy+0.5) h/S - 0.5, 0), sx = max((ox'+0.5) w/S - 0.5, 0)
+//   iy = min(floor(sy), h-1), iy1 = min(iy+1, h-1)   (likewise x: taps clamp to the BOX)
+//   v = bilinear blend of the four taps; out = (v/255 - mean[c]) * inv_std[c]; channel 3 = +0
+// i.e. F.interpolate(crop, (S, S), mode="bilinear", align_corners=False) + flip + normalize.
+//
+// The source coordinate is formed in integers: sy = num / 2S with num = (2 oy + 1) h - S, so
+// floor(sy) and the blend weight rem / 2S are exact up to one fp32 rounding of the weight, and
+// an identity-scale crop (h = S) has weight 0 -- it copies pixels bit for bit.
+//
+// Streaming kernel, no LDS. A workgroup works inside one image, so the box, the gather index
+// and the image base are wave-uniform (scalar loads); a lane produces two adjacent padded
+// pixels of one row and writes them with one 16-byte store (8 bytes for the odd-S row tail).
+// Every tap is one unaligned dword load covering the pixel's three bytes; edge taps use
+// clamped indices, never a branch around a load.
+#include "pdt_common.h"
+
+namespace {
+constexpr int NT = 256;
+
+// One axis of the bilinear sampler: output coordinate o of n source pixels resized to S.
+// S2 = 2S, inv2S = 1 / 2S. (2S+1) n < 2^31 is checked on the host.
+__device__ __forceinline__ void axis_taps(int o, int n, int S, int S2, float inv2S, int& i0, int& i1, float& l) {
+  int num = (2 * o + 1) * n - S;
+  num = num < 0 ? 0 : num;
+  int i = (int)((float)num * inv2S);  // floor(num / 2S) up to +-1: fixed below
+  int r = num - i * S2;
+  if (r < 0) { --i; r += S2; }
+  if (r >= S2) { ++i; r -= S2; }
+  l = (float)r * inv2S;
+  i0 = i < n - 1 ? i : n - 1;
+  i1 = i0 + 1 < n - 1 ? i0 + 1 : n - 1;
+}
+
+// The three bytes of the pixel at byte offset off of an image, in bits 0..23 (R, G, B from the
+// low byte). One unaligned dword load that never leaves the image: bytes [off-1, off+3) for
+// off > 0, bytes [0, 4) for the first pixel (an image has >= 4 bytes, host check).
+__device__ __forceinline__ uint32_t load_rgb(const uint8_t* __restrict__ img, uint32_t off) {
+  const uint32_t back = off > 0 ? 1u : 0u;
+  uint32_t w;
+  __builtin_memcpy(&w, img + (off - back), 4);
+  return w >> (back * 8);
+}
+
+struct PixelOut {
+  uint32_t lo, hi;  // bf16 (c0, c1), (c2, 0)
+};
+
+__device__ __forceinline__ PixelOut sample(const uint8_t* __restrict__ img, uint32_t row0, uint32_t row1, int ix,
+                                           int ix1, float ly, float lx, float m0, float m1, float m2, float s0,
+                                           float s1, float s2) {
+  const uint32_t p00 = load_rgb(img, (row0 + (uint32_t)ix) * 3u);
+  const uint32_t p01 = load_rgb(img, (row0 + (uint32_t)ix1) * 3u);
+  const uint32_t p10 = load_rgb(img, (row1 + (uint32_t)ix) * 3u);
+  const uint32_t p11 = load_rgb(img, (row1 + (uint32_t)ix1) * 3u);
+  const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
+  float v[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float a = (float)((p00 >> (8 * c)) & 0xffu), b = (float)((p01 >> (8 * c)) & 0xffu);
+    const float d = (float)((p10 >> (8 * c)) & 0xffu), e = (float)((p11 >> (8 * c)) & 0xffu);
+    v[c] = fmaf(w11, e, fmaf(w10, d, fmaf(w01, b, w00 * a)));
+  }
+  constexpr float K = 1.f / 255.f;
+  PixelOut o;
+  o.lo = pack2bf((fmaf(v[0], K, -m0)) * s0, (fmaf(v[1], K, -m1)) * s1);
+  o.hi = pack2bf((fmaf(v[2], K, -m2)) * s2, 0.f);
+  return o;
+}
+
+// grid.x = B * nblk: workgroup (b, k) covers pixel pairs [k NT, (k+1) NT) of image b's S * P
+// pairs (P = ceil(S / 2) pairs per output row).
+__global__ void __launch_bounds__(NT)
+crop_resize_norm_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ idx, const int* __restrict__ box,
+                        u16* __restrict__ out, long img_bytes, int Ws, int S, int P, uint32_t nblk, FastDiv dP,
+                        float inv2S, float m0, float m1, float m2, float s0, float s1, float s2) {
+  const uint32_t b = blockIdx.x / nblk;
+  const uint32_t p = (blockIdx.x - b * nblk) * NT + threadIdx.x;
+  if (p >= (uint32_t)(S * P)) return;
+  const int* bx = box + (long)b * 5;
+  const int y0 = bx[0], x0 = bx[1], h = bx[2], w = bx[3], flip = bx[4];
+  const long im = idx ? (long)idx[b] : (long)b;
+  const uint8_t* img = src + im * img_bytes;  // 64-bit image base; offsets inside an image are 32-bit
+
+  const int oy = (int)fdiv(p, dP);
+  const int ox0 = 2 * ((int)p - oy * P);
+  const bool pair = ox0 + 1 < S;
+  const int ox1 = pair ? ox0 + 1 : ox0;  // odd-S tail: the second pixel is computed and dropped
+  const int S2 = 2 * S;
+
+  int iy, iy1;
+  float ly;
+  axis_taps(oy, h, S, S2, inv2S, iy, iy1, ly);
+  const uint32_t row0 = (uint32_t)((y0 + iy) * Ws + x0), row1 = (uint32_t)((y0 + iy1) * Ws + x0);
+
+  int ixa, ixa1, ixb, ixb1;
+  float lxa, lxb;
+  axis_taps(flip ? S - 1 - ox0 : ox0, w, S, S2, inv2S, ixa, ixa1, lxa);
+  axis_taps(flip ? S - 1 - ox1 : ox1, w, S, S2, inv2S, ixb, ixb1, lxb);
+  const PixelOut a = sample(img, row0, row1, ixa, ixa1, ly, lxa, m0, m1, m2, s0, s1, s2);
+  PixelOut c = sample(img, row0, row1, ixb, ixb1, ly, lxb, m0, m1, m2, s0, s1, s2);
+  // pin the second pixel here: left alone, the compiler sinks its four loads into the `pair`
+  // branch below, behind the first pixel's waits (half the loads in flight per lane)
+  asm volatile("" : "+v"(c.lo), "+v"(c.hi));
+
+  // 4 bf16 (8 bytes) per padded pixel; 64-bit pixel index
+  uint2* o = reinterpret_cast<uint2*>(out) + (((long)b * S + oy) * S + ox0);
+  if (pair) {
+    // 8-byte aligned always, 16-byte aligned for even S
+    typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
+    *reinterpret_cast<u32x4_a8*>(o) = u32x4_a8{a.lo, a.hi, c.lo, c.hi};
+  } else {
+    *o = uint2{a.lo, a.hi};
+  }
+}
+}  // namespace
+
+// src: uint8 [n][Hs][Ws][3] (device); idx: int64 [B] source image of each output (device; null:
+// output b reads image b); box: int32 [B][5] = y0, x0, h, w, flip (device); out: bf16
+// [B][S][S][Cp], Cp = 4; mean / inv_std: 3 host floats. The boxes and indices are trusted (the
+// loader validates them on the host before the upload).
+PDT_API int pdt_crop_resize_norm_u8_bf16(const void* src, int Hs, int Ws, const int64_t* idx, const int* box, void* out,
+                                         long B, int S, int Cp, const float* mean, const float* inv_std,
+                                         hipStream_t st) {
+  if (!src || !box || !out || !mean || !inv_std) return -1;
+  if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || Cp != 4) return -1;
+  if (Hs > 32768 || Ws > 32768 || S > 16384) return -1;  // (2S+1) h fits an int
+  const long img_bytes = (long)Hs * Ws * 3;
+  if (img_bytes < 4 || img_bytes >= (1L << 31)) return -1;  // dword taps; 32-bit offsets in an image
+  const int P = (S + 1) / 2;
+  const long nblk = ((long)S * P + NT - 1) / NT;
+  if (B * nblk > 0x7fffffffL) return -1;
+  hipLaunchKernelGGL(crop_resize_norm_kernel, dim3((unsigned)(B * nblk)), dim3(NT), 0, st, (const uint8_t*)src, idx,
+                     box, (u16*)out, img_bytes, Ws, S, P, (uint32_t)nblk, make_fastdiv((uint32_t)P),
+                     1.f / (float)(2 * S), mean[0], mean[1], mean[2], inv_std[0], inv_std[1], inv_std[2]);
+  PDT_RETURN_LAUNCH();
+}

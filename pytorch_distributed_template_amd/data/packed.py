@@ -1,0 +1,464 @@
+"""Real images from a *packed image set*, augmented on the device.
+
+A packed image set is a directory of three files (``scripts/pack_images.py`` builds one per
+split from a class-per-folder image tree; decoding happens once, offline):
+
+* ``images.npy`` -- uint8 ``[N, Hs, Ws, 3]``, C order, RGB, one stored size per set
+  (e.g. 256 x 256); opened with ``np.load(..., mmap_mode="r")``.
+* ``labels.npy`` -- int64 ``[N]``.
+* ``meta.json`` -- ``num_classes``, optional ``classes`` (names), optional ``mean`` / ``std``.
+
+:class:`PackedImageLoader` (``train_loader.type``) is sharded like
+:class:`~.synthetic.SyntheticImageNetLoader` (``DistributedSampler`` in training,
+``set_epoch`` reshuffles; the unpadded :class:`~.samplers.EvalShardSampler` in evaluation)
+and MI355X-first like it: the host moves indices, crop boxes and at most raw uint8 pixels,
+and one HIP launch (``csrc/image_aug.hip``) turns the batch's stored images into the
+random-resized-cropped (training) or center-cropped (evaluation), flipped, normalized bf16
+batch in the zero-padded 4-channel NHWC storage the space-to-depth stem reads in place
+(``pdt_nhwc_pad``). Three modes:
+
+* **resident** -- ``images.npy`` is uploaded to HBM once as uint8; a batch is one small H2D
+  copy (indices, labels, boxes) and one launch that gathers by index.
+* **staged** -- one background thread runs up to ``prefetch`` batches ahead: it gathers the
+  batch's images from the memmap (sorted indices) into a ring of pinned buffers and copies
+  them to a device staging ring on a side stream; the consumer makes its stream wait on the
+  copy's event (no host sync) and launches the same kernel.
+* **torch** -- CPU device, no native library, or a non-bf16 dtype: the same math in torch
+  (per-sample crop + ``F.interpolate`` in fp32).
+
+The augmentation parameters are counter-based: a sample's crop box and flip are a pure
+function of ``(seed, epoch, global sample index)`` -- independent of world size, batch size
+and the sample's position in the batch.
+"""
+from __future__ import annotations
+
+import json
+import math
+import queue
+import threading
+from pathlib import Path
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+from torch.utils.data import DistributedSampler
+
+from ..utils import dist as pdist
+from .samplers import EvalShardSampler
+from .synthetic import _DTYPES, _M32, _default_device, _hash32
+
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+_PACKER_HINT = "build a packed image set with scripts/pack_images.py"
+
+
+class PackedImageSet:
+    """An opened packed image set: ``images`` (uint8 memmap [N, Hs, Ws, 3]), ``labels``
+    (int64 ndarray [N]), ``num_classes``, ``classes`` (names or None), ``mean`` / ``std``
+    (3-tuples or None), ``meta`` (the raw ``meta.json``)."""
+
+    def __init__(self, images, labels, meta):
+        self.images = images
+        self.labels = labels
+        self.meta = meta
+        self.num_classes = int(meta["num_classes"])
+        self.classes = meta.get("classes")
+        self.mean = tuple(float(v) for v in meta["mean"]) if meta.get("mean") is not None else None
+        self.std = tuple(float(v) for v in meta["std"]) if meta.get("std") is not None else None
+
+    def __len__(self):
+        return int(self.images.shape[0])
+
+    def __getitem__(self, i):
+        return torch.from_numpy(np.array(self.images[int(i)])), int(self.labels[int(i)])
+
+    @property
+    def stored_size(self):
+        return int(self.images.shape[1]), int(self.images.shape[2])
+
+
+def open_packed(data_dir) -> PackedImageSet:
+    """Open and validate the packed image set in ``data_dir``."""
+    d = Path(data_dir)
+    if not d.is_dir():
+        raise FileNotFoundError(f"packed image set not found: {d} is not a directory -- {_PACKER_HINT}")
+    for name in ("images.npy", "labels.npy", "meta.json"):
+        if not (d / name).is_file():
+            raise FileNotFoundError(f"packed image set {d} has no {name} -- {_PACKER_HINT}")
+    images = np.load(d / "images.npy", mmap_mode="r")
+    labels = np.load(d / "labels.npy")
+    meta = json.loads((d / "meta.json").read_text())
+    if images.dtype != np.uint8:
+        raise ValueError(f"{d}/images.npy: dtype must be uint8, got {images.dtype}")
+    if images.ndim != 4:
+        raise ValueError(f"{d}/images.npy: shape must be [N, H, W, 3], got rank {images.ndim}")
+    if images.shape[3] != 3:
+        raise ValueError(f"{d}/images.npy: images must have 3 channels (RGB), got {images.shape[3]}")
+    if not images.flags["C_CONTIGUOUS"] or images.shape[0] == 0:
+        raise ValueError(f"{d}/images.npy: must be a non-empty C-order array")
+    if labels.dtype != np.int64 or labels.ndim != 1:
+        raise ValueError(f"{d}/labels.npy: must be int64 [N], got {labels.dtype} rank {labels.ndim}")
+    if labels.shape[0] != images.shape[0]:
+        raise ValueError(f"{d}: {images.shape[0]} images but {labels.shape[0]} labels")
+    if not isinstance(meta, dict) or "num_classes" not in meta:
+        raise ValueError(f"{d}/meta.json: must be an object with num_classes")
+    nc = int(meta["num_classes"])
+    if labels.min() < 0 or labels.max() >= nc:
+        raise ValueError(f"{d}/labels.npy: labels must lie in [0, num_classes={nc})")
+    for key in ("mean", "std"):
+        if meta.get(key) is not None and len(meta[key]) != 3:
+            raise ValueError(f"{d}/meta.json: {key} must have 3 entries")
+    return PackedImageSet(images, labels, meta)
+
+
+# ----------------------------------------------------------------------------- boxes
+_TRIES = 10
+_DRAWS = 4 * _TRIES + 1  # (area, ratio, y, x) per try, then the flip
+
+
+def _uniforms(indices, epoch, seed) -> torch.Tensor:
+    """float64 [B, _DRAWS] in [0, 1): draw j of sample i is a hash of (seed, epoch, i, j)."""
+    idx = torch.as_tensor(indices, dtype=torch.int64).reshape(-1)
+    s = _hash32(((idx & _M32) * 0x9E3779B9 & _M32) ^ (int(seed) & _M32))
+    s = _hash32(s ^ ((int(epoch) & _M32) * 0x85EBCA6B & _M32) ^ ((idx >> 32) & _M32))
+    j = torch.arange(1, _DRAWS + 1, dtype=torch.int64)
+    h = _hash32(((j * 0xC2B2AE35) & _M32)[None, :] ^ s[:, None])
+    return (h >> 8).to(torch.float64) / 16777216.0
+
+
+def random_resized_crop_boxes(indices, epoch, seed, Hs, Ws, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3),
+                              hflip=0.5) -> torch.Tensor:
+    """int32 [B, 5] = (y0, x0, h, w, flip) for global sample ``indices``: torchvision's
+    RandomResizedCrop on an ``Hs x Ws`` image -- up to 10 tries of area = Hs Ws U(scale), a
+    log-uniform aspect ratio, ``w = round(sqrt(area r))``, ``h = round(sqrt(area / r))``,
+    accepted when the box fits, then a uniform offset; otherwise the center crop clipped to
+    the ratio bounds -- plus a horizontal flip with probability ``hflip``. Each row is a pure
+    function of ``(seed, epoch, index)``."""
+    Hs, Ws = int(Hs), int(Ws)
+    u = _uniforms(indices, epoch, seed)
+    B = u.shape[0]
+    t = u[:, :4 * _TRIES].reshape(B, _TRIES, 4)
+    area = Hs * Ws * (scale[0] + t[..., 0] * (scale[1] - scale[0]))
+    lr0, lr1 = math.log(ratio[0]), math.log(ratio[1])
+    ar = torch.exp(lr0 + t[..., 1] * (lr1 - lr0))
+    w = torch.round(torch.sqrt(area * ar)).to(torch.int64)
+    h = torch.round(torch.sqrt(area / ar)).to(torch.int64)
+    ok = (w > 0) & (w <= Ws) & (h > 0) & (h <= Hs)
+    first = torch.argmax(ok.to(torch.int64), dim=1)  # first accepted try (0 when none is)
+    rows = torch.arange(B)
+    w, h = w[rows, first], h[rows, first]
+    y0 = torch.floor(t[rows, first, 2] * (Hs - h + 1).clamp(min=1)).to(torch.int64)
+    x0 = torch.floor(t[rows, first, 3] * (Ws - w + 1).clamp(min=1)).to(torch.int64)
+    # fallback: the center crop with the aspect ratio clipped to the bounds
+    in_ratio = Ws / Hs
+    if in_ratio < ratio[0]:
+        fw, fh = Ws, int(round(Ws / ratio[0]))
+    elif in_ratio > ratio[1]:
+        fh, fw = Hs, int(round(Hs * ratio[1]))
+    else:
+        fw, fh = Ws, Hs
+    fw, fh = min(max(fw, 1), Ws), min(max(fh, 1), Hs)
+    none = ~ok.any(dim=1)
+    h = torch.where(none, torch.full_like(h, fh), h)
+    w = torch.where(none, torch.full_like(w, fw), w)
+    y0 = torch.where(none, torch.full_like(y0, (Hs - fh) // 2), y0)
+    x0 = torch.where(none, torch.full_like(x0, (Ws - fw) // 2), x0)
+    flip = (u[:, -1] < float(hflip)).to(torch.int64)
+    return torch.stack([y0, x0, h, w, flip], dim=1).to(torch.int32)
+
+
+def center_crop_boxes(B, Hs, Ws, crop_fraction=0.875) -> torch.Tensor:
+    """int32 [B, 5]: the centered ``round(Hs f) x round(Ws f)`` box, no flip (evaluation). A
+    256 store with ``f = 0.875`` gives the 224 x 224 box at (16, 16): at image size 224 the
+    resize is the identity."""
+    h = min(max(int(round(Hs * crop_fraction)), 1), int(Hs))
+    w = min(max(int(round(Ws * crop_fraction)), 1), int(Ws))
+    row = torch.tensor([(Hs - h) // 2, (Ws - w) // 2, h, w, 0], dtype=torch.int32)
+    return row.repeat(int(B), 1)
+
+
+def validate_boxes(box, Hs, Ws):
+    """Raise unless every box lies inside the ``Hs x Ws`` image with ``h, w >= 1`` (the
+    kernel trusts its boxes)."""
+    b = box.to(torch.int64)
+    y0, x0, h, w = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
+    bad = (y0 < 0) | (x0 < 0) | (h < 1) | (w < 1) | (y0 + h > Hs) | (x0 + w > Ws)
+    if bool(bad.any()):
+        i = int(torch.nonzero(bad)[0])
+        raise ValueError(f"crop box {box[i].tolist()} of batch entry {i} is outside the {Hs}x{Ws} image")
+
+
+def validate_indices(indices, n):
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    if idx.size and (idx.min() < 0 or idx.max() >= n):
+        raise IndexError(f"sample index out of range for a packed image set of {n} images: "
+                         f"[{int(idx.min())}, {int(idx.max())}]")
+    return idx
+
+
+def crop_resize_normalize_torch(images, box, S, mean, std, dtype=torch.float32):
+    """The kernel's math in torch: ``images`` uint8 [B, Hs, Ws, 3] -> [B, 3, S, S] ``dtype``
+    (computed in fp32): per-sample crop, bilinear ``F.interpolate`` (``align_corners=False``, no
+    antialias), horizontal flip, ``(v / 255 - mean) / std``."""
+    m = torch.tensor(mean, dtype=torch.float32).view(1, 3, 1, 1)
+    s = torch.tensor(std, dtype=torch.float32).view(1, 3, 1, 1)
+    out = []
+    for img, (y0, x0, h, w, flip) in zip(images, box.tolist()):
+        crop = img[y0:y0 + h, x0:x0 + w].permute(2, 0, 1)[None].to(torch.float32)
+        r = F.interpolate(crop, size=(S, S), mode="bilinear", align_corners=False, antialias=False)
+        if flip:
+            r = r.flip(3)
+        out.append((r / 255.0 - m) / s)
+    return torch.cat(out).to(dtype)
+
+
+# ----------------------------------------------------------------------------- loader
+class PackedImageLoader:
+    """Config-facing loader over a packed image set (see the module docstring).
+
+    Yields ``(images [B, 3, S, S], labels int64 [B])`` on ``device``. On the native path
+    (CUDA device, kernel library present, bf16, ``channels_last``) ``images`` is a view into
+    bf16 ``[B, S, S, 4]`` tagged ``pdt_nhwc_pad = 4``; otherwise the torch path returns
+    ``dtype`` (``channels_last`` strides when asked).
+
+    ``mean`` / ``std``: the arguments, else ``meta.json``'s, else the ImageNet constants.
+    ``resident``: True, False or ``"auto"`` (resident when ``images.npy`` is at most
+    ``resident_limit_gb``). ``num_workers`` is accepted and ignored: there are no worker
+    processes."""
+
+    def __init__(self, data_dir, batch_size, training=True, image_size=224, shuffle=True, seed=0,
+                 scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), hflip=0.5, crop_fraction=0.875, mean=None, std=None,
+                 resident="auto", resident_limit_gb=16, prefetch=2, dtype=None, channels_last=True, device=None,
+                 num_workers=0):
+        self.dataset = open_packed(data_dir)
+        ds = self.dataset
+        self.batch_size = int(batch_size)
+        self.training = bool(training)
+        self.image_size = int(image_size)
+        self.seed = int(seed)
+        self.scale, self.ratio, self.hflip = tuple(scale), tuple(ratio), float(hflip)
+        self.crop_fraction = float(crop_fraction)
+        self.mean = tuple(mean) if mean is not None else (ds.mean or IMAGENET_MEAN)
+        self.std = tuple(std) if std is not None else (ds.std or IMAGENET_STD)
+        assert len(self.mean) == 3 and len(self.std) == 3 and all(s > 0 for s in self.std)
+        self.device = torch.device(device) if device is not None else _default_device()
+        if dtype is None:
+            dtype = "bfloat16" if self.device.type == "cuda" else "float32"
+        self.dtype = _DTYPES[dtype] if isinstance(dtype, str) else dtype
+        self.channels_last = bool(channels_last)
+        self.prefetch = max(1, int(prefetch))
+        self.epoch = 0
+
+        rank, world = pdist.get_rank(), pdist.get_world_size()
+        if self.training:
+            self.sampler = DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=shuffle, seed=self.seed)
+        else:
+            self.sampler = EvalShardSampler(ds, rank=rank, world_size=world)
+        self.n_samples = len(self.sampler)
+
+        if resident not in (True, False, "auto"):
+            raise ValueError(f"resident must be true, false or 'auto', got {resident!r}")
+        self.native = self._native()
+        if not self.native:
+            self.mode = "torch"
+        elif resident is True or (resident == "auto" and ds.images.nbytes <= float(resident_limit_gb) * 2 ** 30):
+            self.mode = "resident"
+        else:
+            self.mode = "staged"
+        self._src = None        # resident: the whole set on the device
+        self._ring = None       # staged: [(pinned, device)] slots
+        self._side = None
+        self._copied = None
+        self._stage_thread = None  # staged: the pass under way (the ring serves one at a time)
+
+    # ------------------------------------------------------------------ surface
+    def _native(self) -> bool:
+        if self.device.type != "cuda" or self.dtype != torch.bfloat16 or not self.channels_last:
+            return False
+        from ..ops import native_ops
+        return native_ops.available()
+
+    def __len__(self):
+        return math.ceil(self.n_samples / self.batch_size)
+
+    def set_epoch(self, epoch: int):
+        self.epoch = int(epoch)
+        self.sampler.set_epoch(self.epoch)
+
+    def _index_batches(self):
+        idx = list(self.sampler)
+        return [idx[i:i + self.batch_size] for i in range(0, len(idx), self.batch_size)]
+
+    def boxes(self, indices, epoch=None) -> torch.Tensor:
+        """The validated crop boxes (int32 [B, 5], host) of global sample ``indices`` in ``epoch``
+        (default: the current one)."""
+        Hs, Ws = self.dataset.stored_size
+        if self.training:
+            box = random_resized_crop_boxes(indices, self.epoch if epoch is None else epoch, self.seed, Hs, Ws,
+                                            self.scale, self.ratio, self.hflip)
+        else:
+            box = center_crop_boxes(len(indices), Hs, Ws, self.crop_fraction)
+        validate_boxes(box, Hs, Ws)
+        return box
+
+    def __iter__(self):
+        if self.mode == "torch":
+            return self._iter_torch()
+        if self.mode == "resident":
+            return self._iter_resident()
+        return self._iter_staged()
+
+    # ------------------------------------------------------------------ torch path
+    def _iter_torch(self):
+        ds = self.dataset
+        fmt = torch.channels_last if self.channels_last else torch.contiguous_format
+        epoch = self.epoch  # one pass, one epoch's boxes, whatever set_epoch does meanwhile
+        for indices in self._index_batches():
+            idx = validate_indices(indices, len(ds))
+            box = self.boxes(indices, epoch)
+            order = np.argsort(idx, kind="stable")
+            imgs = np.empty((len(idx),) + ds.images.shape[1:], dtype=np.uint8)
+            imgs[order] = ds.images[idx[order]]
+            x = crop_resize_normalize_torch(torch.from_numpy(imgs), box, self.image_size, self.mean, self.std,
+                                            self.dtype)
+            y = torch.from_numpy(ds.labels[idx])
+            yield x.contiguous(memory_format=fmt).to(self.device), y.to(self.device)
+
+    # ------------------------------------------------------------------ native paths
+    def _upload_params(self, kidx, labels, box):
+        """One small H2D copy: kernel gather indices, labels (int64 [B] each) and boxes (int32
+        [B, 5]) in one pinned buffer. Returns the three device views."""
+        B = len(kidx)
+        host = torch.empty(9 * B, dtype=torch.int32, pin_memory=True)
+        host[:2 * B].view(torch.int64).copy_(torch.from_numpy(np.ascontiguousarray(kidx, dtype=np.int64)))
+        host[2 * B:4 * B].view(torch.int64).copy_(torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int64)))
+        host[4 * B:].view(B, 5).copy_(box)
+        dev = host.to(self.device, non_blocking=True)
+        return dev[:2 * B].view(torch.int64), dev[2 * B:4 * B].view(torch.int64), dev[4 * B:].view(B, 5)
+
+    def _launch(self, src, kidx, box):
+        from ..ops import native_ops
+        B, S = box.shape[0], self.image_size
+        buf = torch.empty((B, S, S, 4), dtype=torch.bfloat16, device=self.device)
+        native_ops.crop_resize_normalize(src, kidx, box, buf, self.mean, self.std)
+        x = buf[..., :3].permute(0, 3, 1, 2)
+        x.pdt_nhwc_pad = 4
+        return x
+
+    def _resident_src(self):
+        if self._src is None:
+            im = self.dataset.images
+            src = torch.empty(im.shape, dtype=torch.uint8, device=self.device)
+            step = max(1, (256 << 20) // max(1, im[0].nbytes))  # 256-MB pieces: host memory stays flat
+            for i in range(0, im.shape[0], step):
+                src[i:i + step].copy_(torch.from_numpy(np.array(im[i:i + step])))
+            self._src = src
+        return self._src
+
+    def _iter_resident(self):
+        ds = self.dataset
+        src = self._resident_src()
+        epoch = self.epoch
+        for indices in self._index_batches():
+            idx = validate_indices(indices, len(ds))
+            kidx, y, box = self._upload_params(idx, ds.labels[idx], self.boxes(indices, epoch))
+            yield self._launch(src, kidx, box), y
+
+    def _staging_ring(self):
+        if self._ring is None:
+            shape = (self.batch_size,) + tuple(self.dataset.images.shape[1:])
+            self._ring = [(torch.empty(shape, dtype=torch.uint8, pin_memory=True),
+                           torch.empty(shape, dtype=torch.uint8, device=self.device))
+                          for _ in range(self.prefetch + 1)]
+            self._side = torch.cuda.Stream(device=self.device)
+            # each slot's last H2D copy, kept across passes: the next pass must not gather into a
+            # pinned slot whose copy from the previous pass is still queued (inf_loop starts the
+            # next pass at once, and the device runs steps behind the host)
+            self._copied = [None] * len(self._ring)
+        return self._ring
+
+    def _iter_staged(self):
+        ds = self.dataset
+        if self._stage_thread is not None and self._stage_thread.is_alive():
+            raise RuntimeError("PackedImageLoader (staged): a pass is still under way -- its staging ring "
+                               "serves one pass at a time; finish or drop that iterator first")
+        ring = self._staging_ring()
+        side = self._side
+        batches = self._index_batches()
+        epoch = self.epoch  # the producer runs ahead: set_epoch must not change a pass under way
+        nslots = len(ring)
+        ready = queue.Queue(maxsize=self.prefetch)
+        stop = threading.Event()
+        released = [threading.Event() for _ in range(nslots)]  # the consumer launched on this slot
+        release_ev = [None] * nslots                           # ... and this event follows its kernel
+        copied = self._copied                                   # the slot's last H2D copy (any pass)
+        # the device staging buffers may still be read by kernels of the previous pass
+        side.wait_stream(torch.cuda.current_stream(self.device))
+
+        def put(item):
+            while not stop.is_set():
+                try:
+                    ready.put(item, timeout=0.05)
+                    return True
+                except queue.Full:
+                    pass
+            return False
+
+        def produce():
+            try:
+                torch.cuda.set_device(self.device)
+                for n, indices in enumerate(batches):
+                    slot = n % nslots
+                    pinned, staged = ring[slot]
+                    if n >= nslots:
+                        while not released[slot].wait(0.05):
+                            if stop.is_set():
+                                return
+                        released[slot].clear()
+                        side.wait_event(release_ev[slot])  # the device slot's last reader
+                    if copied[slot] is not None:
+                        # the pinned slot's last copy, of this pass or the one before: a host wait
+                        # in this thread only
+                        copied[slot].synchronize()
+                    idx = validate_indices(indices, len(ds))
+                    box = self.boxes(indices, epoch)
+                    order = np.argsort(idx, kind="stable")
+                    B = len(idx)
+                    np.take(ds.images, idx[order], axis=0, out=pinned[:B].numpy())
+                    kidx = np.empty(B, dtype=np.int64)
+                    kidx[order] = np.arange(B, dtype=np.int64)  # output b reads staged image kidx[b]
+                    with torch.cuda.stream(side):
+                        staged[:B].copy_(pinned[:B], non_blocking=True)
+                        ev = torch.cuda.Event()
+                        ev.record(side)
+                    copied[slot] = ev
+                    if not put(("batch", slot, B, kidx, ds.labels[idx], box, ev)):
+                        return
+                put(("end",))
+            except BaseException as e:  # re-raised in the consumer
+                put(("error", e))
+
+        thread = threading.Thread(target=produce, name="PackedImageLoader-stage", daemon=True)
+        thread.start()
+        self._stage_thread = thread
+        try:
+            while True:
+                item = ready.get()
+                if item[0] == "end":
+                    break
+                if item[0] == "error":
+                    raise item[1]
+                _, slot, B, kidx, labels, box, ev = item
+                cur = torch.cuda.current_stream(self.device)
+                cur.wait_event(ev)
+                kidx_d, y, box_d = self._upload_params(kidx, labels, box)
+                x = self._launch(ring[slot][1], kidx_d, box_d)
+                rel = torch.cuda.Event()
+                rel.record(cur)
+                release_ev[slot] = rel
+                released[slot].set()
+                yield x, y
+        finally:
+            stop.set()
+            thread.join(timeout=10)
+            torch.cuda.current_stream(self.device).wait_stream(side)

@@ -118,6 +118,7 @@ _SIGS = {
     "pdt_fill_uniform_bf16": (c_int, [P, c_long, c_uint, P]),
     "pdt_cast_f32_bf16": (c_int, [P, P, c_long, P]),
     "pdt_synth_images_bf16": (c_int, [P, P, c_long, c_int, c_int, c_int, c_uint, P, c_int, P]),
+    "pdt_crop_resize_norm_u8_bf16": (c_int, [P, c_int, c_int, P, P, P, c_long, c_int, c_int, P, P, P]),
     "pdt_lane_reduce_probe": (c_int, [P, P, c_int, P]),
     "pdt_wt_dgrad": (c_int, [P, P] + [c_int] * 9 + [P]),
     "pdt_transpose_cast": (c_int, [P, P, c_int, c_int, P]),
@@ -834,6 +835,33 @@ def synthetic_images_at(buf, idx, C, seed, labels, num_classes):
     assert labels.dtype == torch.int64 and labels.numel() == B and labels.device == buf.device
     _chk(_load().pdt_synth_images_bf16(_p(buf), _p(idx), B, H * W, C, Cp, seed & 0xFFFFFFFF, _p(labels),
                                        int(num_classes), _s()), "synth_images")
+
+
+def crop_resize_normalize(src, idx, box, out, mean, std):
+    """The packed-image input pipeline in one launch (``csrc/image_aug.hip``): output ``b`` is the
+    crop ``box[b] = (y0, x0, h, w, flip)`` of stored image ``idx[b]`` (``idx`` None: image ``b``),
+    resized bilinearly (``align_corners=False``, no antialias) to ``S x S``, flipped horizontally
+    when ``flip``, and normalized ``(v / 255 - mean[c]) / std[c]``.
+
+    ``src`` uint8 [n, Hs, Ws, 3]; ``idx`` int64 [B] or None; ``box`` int32 [B, 5]; ``out`` bf16
+    [B, S, S, Cp] (channel 3 is written as 0); all on one device. ``mean`` / ``std``: 3 floats.
+    The kernel trusts the boxes and indices: validate them on the host (``data/packed.py``)."""
+    assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and src.is_contiguous()
+    assert out.dtype == torch.bfloat16 and out.dim() == 4 and out.is_contiguous() and out.device == src.device
+    B, S, S2, Cp = out.shape
+    assert S == S2 and Cp % 4 == 0 and B > 0
+    assert box.dtype == torch.int32 and tuple(box.shape) == (B, 5) and box.is_contiguous() and box.device == src.device
+    if idx is not None:
+        assert idx.dtype == torch.int64 and tuple(idx.shape) == (B,) and idx.is_contiguous() \
+            and idx.device == src.device
+    else:
+        assert src.shape[0] >= B
+    assert len(mean) == 3 and len(std) == 3 and all(float(s) > 0 for s in std)
+    m = (c_float * 3)(*[float(v) for v in mean])
+    inv = (c_float * 3)(*[1.0 / float(v) for v in std])
+    n, Hs, Ws, _ = src.shape
+    _chk(_load().pdt_crop_resize_norm_u8_bf16(_p(src), Hs, Ws, _p(idx), _p(box), _p(out), B, S, Cp,
+                                              ctypes.addressof(m), ctypes.addressof(inv), _s()), "crop_resize_norm")
 
 
 def synthetic_images(shape, dtype, device, seed=0, channels_last=True):
