@@ -20,6 +20,8 @@ from pathlib import Path
 import torch
 import torch.nn as nn
 
+from . import autotune
+
 _LIB_PATH = Path(os.environ.get("PDT_LIB_PATH", "") or
                  Path(__file__).resolve().parents[1] / "_lib" / "libpdt_hip.so")  # override: A/B builds
 _lib = None
@@ -362,72 +364,10 @@ def _weak(t):
 # =============================================================================
 # raw kernel wrappers
 # =============================================================================
-# -----------------------------------------------------------------------------
-# Tile-variant autotuner: the first eager call of every distinct geometry times
-# each tile variant (csrc/conv_igemm.hip, conv_wgrad.hip) with HIP events and
-# keeps the fastest.
-#   * The shipped table (_lib/autotune_gfx950.json, tracked) is READ-ONLY at run
-#     time; new entries go to a per-user cache (PDT_AUTOTUNE_CACHE, default
-#     ~/.cache/pytorch_distributed_template_amd/autotune_gfx950.json) overlaid
-#     on it at load.
-#   * PDT_AUTOTUNE=0 or --deterministic (PDT_DETERMINISTIC=1): no timing at all --
-#     shipped/cached choices, else the fixed heuristic, so every run and every
-#     rank picks the same variant (and the same split-K summation order).
-#   * World size > 1: ranks must not time variants independently (different
-#     choices per rank, stragglers inside the first backward). Tuning is off
-#     unless :func:`pretune_distributed` runs: rank 0 tunes on one step and
-#     broadcasts its table, then every rank freezes it.
-# -----------------------------------------------------------------------------
-_SHIPPED_TUNE_PATH = _LIB_PATH.parent / "autotune_gfx950.json"
-_TUNE_PATH = Path(os.environ.get("PDT_AUTOTUNE_CACHE", str(Path.home() / ".cache" / "pytorch_distributed_template_amd"
-                                                          / "autotune_gfx950.json")))
-_TUNED: dict | None = None
-_TUNE_FORCE = False   # pretune_distributed: rank 0 tunes although WORLD_SIZE > 1
-_TUNE_FROZEN = False  # after the broadcast: no rank tunes any more
-
-
-def _tuned() -> dict:
-    global _TUNED
-    if _TUNED is None:
-        import json
-        table = {}
-        # PDT_AUTOTUNE_SHIPPED=0: ignore the shipped table (re-tuning experiments)
-        paths = (_SHIPPED_TUNE_PATH, _TUNE_PATH) if os.environ.get("PDT_AUTOTUNE_SHIPPED", "1") != "0" \
-            else (_TUNE_PATH,)
-        for path in paths:
-            try:
-                table.update(json.loads(Path(path).read_text()))
-            except Exception:
-                pass
-        _TUNED = table
-    return _TUNED
-
-
-def _save_tuned():
-    """Persist the table to the user cache (never the installed package)."""
-    if os.environ.get("RANK", "0") != "0" or _TUNE_PATH.resolve() == _SHIPPED_TUNE_PATH.resolve():
-        return
-    try:
-        import json
-        _TUNE_PATH.parent.mkdir(parents=True, exist_ok=True)
-        tmp = str(_TUNE_PATH) + f".tmp{os.getpid()}"
-        with open(tmp, "w") as f:
-            json.dump(_TUNED, f, indent=0, sort_keys=True)
-        os.replace(tmp, _TUNE_PATH)
-    except Exception:
-        pass
-
-
-def _capturing() -> bool:
-    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-
-
-def _tune_allowed() -> bool:
-    if _TUNE_FROZEN or _capturing():
-        return False
-    if os.environ.get("PDT_AUTOTUNE", "1") == "0" or os.environ.get("PDT_DETERMINISTIC", "0") == "1":
-        return False
-    return _TUNE_FORCE or int(os.environ.get("WORLD_SIZE", "1")) <= 1
+# Tile-variant autotuner: table, policy, timing and the selection protocol live in
+# ``ops/autotune.py`` (``autotune.choose``); a site here gives it a key, a launch and a default.
+_tuned, _tune_allowed, _capturing = autotune.tuned, autotune.tune_allowed, autotune.capturing
+NOT_APPLICABLE, AX_UNFUSED = autotune.NOT_APPLICABLE, autotune.AX_UNFUSED
 
 
 def pretune_distributed(run_step) -> None:
@@ -437,30 +377,27 @@ def pretune_distributed(run_step) -> None:
     DDP-wrapped). Rank 0 runs it with tuning enabled, then broadcasts its table;
     every rank adopts it and tuning is frozen (untuned shapes later fall back to
     the deterministic heuristic on every rank alike)."""
-    global _TUNE_FORCE, _TUNE_FROZEN
     import torch.distributed as dist
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
         return
     obj = [None]
     if dist.get_rank() == 0:
-        tune_on = os.environ.get("PDT_AUTOTUNE", "1") != "0" and os.environ.get("PDT_DETERMINISTIC", "0") != "1"
         err = None
-        if tune_on:
+        if os.environ.get("PDT_AUTOTUNE", "1") != "0" and os.environ.get("PDT_DETERMINISTIC", "0") != "1":
             # the step must leave no trace on rank 0 that the other ranks do not share:
             # RNG streams are restored (DataLoader seeds, dropout), the fp8 scaling
             # histories it created or rolled are dropped (``_snapshot_fp8_meta``)
             cpu_rng = torch.get_rng_state()
             cuda_rng = torch.cuda.get_rng_state() if torch.cuda.is_available() else None
             fp8_before = _snapshot_fp8_meta()
-            _TUNE_FORCE = True
             try:
-                run_step()
-                if torch.cuda.is_available():
-                    torch.cuda.synchronize()
+                with autotune.forced_tuning():
+                    run_step()
+                    if torch.cuda.is_available():
+                        torch.cuda.synchronize()
             except Exception as e:  # tell the other ranks instead of leaving them in the broadcast
                 err = f"{type(e).__name__}: {e}"
             finally:
-                _TUNE_FORCE = False
                 torch.set_rng_state(cpu_rng)
                 if cuda_rng is not None:
                     torch.cuda.set_rng_state(cuda_rng)
@@ -469,9 +406,7 @@ def pretune_distributed(run_step) -> None:
     dist.broadcast_object_list(obj, src=0)
     if isinstance(obj[0], dict) and set(obj[0]) == {"error"}:
         raise RuntimeError(f"kernel pre-tuning step failed on rank 0: {obj[0]['error']}")
-    _tuned().clear()
-    _tuned().update(obj[0])
-    _TUNE_FROZEN = True
+    autotune.adopt(obj[0])
 
 
 _FP8_META_ATTRS = ("_pdt_fp8_meta", "_pdt_fp8_gmeta")
@@ -506,9 +441,6 @@ def _restore_fp8_meta(snap):
                 delattr(obj, a)
 
 
-NOT_APPLICABLE = -5  # kernel return code: this variant cannot run this geometry
-
-
 class NotApplicable(RuntimeError):
     """An explicitly requested kernel variant cannot run this geometry / epilogue."""
 
@@ -517,78 +449,6 @@ def _chk_v(rc, name):
     if rc == NOT_APPLICABLE:
         raise NotApplicable(f"{name}: variant not applicable")
     _chk(rc, name)
-
-
-def _time_variants(nvar, launch, allowed=None):
-    """Fastest variant id: one warm launch each, then two interleaved rounds over all
-    variants of a 3-launch HIP-event trial, best trial per variant (interleaving keeps a
-    clock / cache transient from favouring whichever variants happen to run first)."""
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    cand = []
-    for v in range(nvar):
-        if allowed is not None and v not in allowed:
-            continue
-        rc = launch(v)
-        if rc == NOT_APPLICABLE:  # e.g. the streaming 1x1 kernel on a 3x3 geometry
-            continue
-        _chk(rc, f"tune variant {v}")
-        cand.append(v)
-    if not cand:
-        return -1
-    best_t = {v: float("inf") for v in cand}
-    # PDT_TUNE_ROUNDS (default 2): interleaved rounds; more rounds cut the timing noise of a
-    # (re)tune run at the cost of its length
-    for _ in range(max(1, int(os.environ.get("PDT_TUNE_ROUNDS", "2")))):
-        for v in cand:
-            ev0.record()
-            for _ in range(3):
-                launch(v)
-            ev1.record()
-            ev1.synchronize()
-            best_t[v] = min(best_t[v], ev0.elapsed_time(ev1))
-    return min(cand, key=lambda v: best_t[v])
-
-
-def _autotune(key, nvar, launch, default=0):
-    table = _tuned()
-    if key in table:
-        return int(table[key])
-    if not _tune_allowed():
-        return default
-    table[key] = _time_variants(nvar, launch)
-    _save_tuned()
-    return table[key]
-
-
-def _id_set(spec):
-    out = set()
-    for part in spec.split(","):
-        lo, _, hi = part.partition("-")
-        out.update(range(int(lo), int(hi or lo) + 1))
-    return out
-
-
-def _variant_filter():
-    """PDT_NT_VARIANTS="0-29,31" restricts the conv_nt variants the tuner may pick."""
-    spec = os.environ.get("PDT_NT_VARIANTS")
-    return _id_set(spec) if spec else None
-
-
-_RETUNED: set = set()
-
-
-def _retune_candidates(key, table):
-    """PDT_RETUNE_WITH="45-48": a targeted re-tune of the table -- every conv_nt key already in
-    it is timed once more against these new variant ids only (its current choice included),
-    and switches when one of them is faster (PDT_RETUNE_PREFIX: only the keys of one family).
-    Returns the allowed id set, or None (no re-tune)."""
-    spec = os.environ.get("PDT_RETUNE_WITH")
-    if not spec or key in _RETUNED or key not in table or not _tune_allowed():
-        return None
-    if not key.startswith(os.environ.get("PDT_RETUNE_PREFIX", "")):  # e.g. "ntb2:" (one key family)
-        return None
-    _RETUNED.add(key)
-    return _id_set(spec) | {int(table[key])}
 
 
 def _nt_args(src, b, out, stats, bias, a, act, variant, addend=None, aux=None, addend_mask=None):
@@ -622,41 +482,26 @@ def _check_nt(src, b, out, a):
     assert a["Nimg"] * a["Hs"] * a["Ws"] < 2 ** 31 and a["Nimg"] * a["Ho"] * a["Wo"] < 2 ** 31
 
 
-_NT_KEYS: dict = {}  # geometry tuple -> tuned-table key string (built once per geometry)
-
-
 def select_nt_variant(src, b, out, *, with_stats=False, bias=None, act=0, aux=None, addend=None, **a):
     """Variant id for this geometry and epilogue (tuning it on first use when allowed)."""
-    M = a["Nimg"] * a["Hm"] * a["Wm"]
-    geom = (a["Hs"], a["Ws"], a["Cs"], a["Nimg"], a["Hm"], a["Wm"], a["Ncol"], a["K"], a["sh"], a["sw"], a["nth"],
-            a["ntw"], a["osh"], int(with_stats), int(bias is not None), a.get("pix", 0), int(act))
-    key = _NT_KEYS.get(geom)
-    if key is None:
-        key = "nt5:" + ",".join(str(x) for x in geom[:15])
-        if a.get("pix"):
-            key += f",p{a['pix']}"
-        if act:  # epilogue work changes the best tile (and the streaming 1x1 kernels take no activation)
-            key += f",a{int(act)}"
-        _NT_KEYS[geom] = key
-    table = _tuned()
-    allowed = _retune_candidates(key, table)
-    if key in table and allowed is None:
-        return int(table[key])
-    lib = _load()
-    if not _tune_allowed():
-        return lib.pdt_conv_nt_resolve_variant(-1, M, a["Ncol"], a["K"])
-    _check_nt(src, b, out, a)
-    nvar = lib.pdt_conv_nt_num_variants()
-    # partial-stat rows depend on the variant's BM and waves-along-M: size for the largest
-    rows = max(lib.pdt_conv_nt_stat_rows(M, a["Ncol"], a["K"], v) for v in range(nvar))
-    stats = torch.empty(2 * rows * a["Ncol"], dtype=torch.float32, device=src.device) if with_stats else None
-    tune_add = addend if act in (3, 5) else None  # acts 3 / 5 read their operand through the addend pointer
-    best = _time_variants(nvar, lambda v: lib.pdt_conv_nt(*_nt_args(src, b, out, stats, bias, a, act, v, aux=aux,
-                                                                    addend=tune_add)),
-                          allowed if allowed is not None else _variant_filter())
-    table[key] = best
-    _save_tuned()
-    return best
+    M, Ncol, K = a["Nimg"] * a["Hm"] * a["Wm"], a["Ncol"], a["K"]
+
+    def setup():
+        lib = _load()
+        _check_nt(src, b, out, a)
+        ids = range(lib.pdt_conv_nt_num_variants())
+        # partial-stat rows depend on the variant's BM and waves-along-M: size for the largest
+        rows = max(lib.pdt_conv_nt_stat_rows(M, Ncol, K, v) for v in ids)
+        stats = torch.empty(2 * rows * Ncol, dtype=torch.float32, device=src.device) if with_stats else None
+        tune_add = addend if act in (3, 5) else None  # acts 3 / 5 read their operand through the addend pointer
+        return ids, lambda v: lib.pdt_conv_nt(*_nt_args(src, b, out, stats, bias, a, act, v, aux=aux,
+                                                        addend=tune_add))
+
+    return autotune.choose(
+        autotune.nt_key(a["Hs"], a["Ws"], a["Cs"], a["Nimg"], a["Hm"], a["Wm"], Ncol, K, a["sh"], a["sw"], a["nth"],
+                        a["ntw"], a["osh"], with_stats, bias is not None, a.get("pix", 0), act),
+        setup, lambda: _load().pdt_conv_nt_resolve_variant(-1, M, Ncol, K),
+        retune="PDT_RETUNE_WITH", first_only="PDT_NT_VARIANTS")
 
 
 ACT = {None: 0, "none": 0, "relu": 1, "gelu": 2}
@@ -677,8 +522,7 @@ def conv_nt(src, b, out, *, stats=None, bias=None, relu=False, act=None, variant
     """C[m, n] = sum_k A[m, k] B[n, k] (+ addend) with the implicit-GEMM gather (see csrc/conv_igemm.hip)."""
     _check_nt(src, b, out, a)
     if addend is not None:
-        assert addend.dtype == torch.bfloat16 and addend.numel() == out.numel() and addend.is_contiguous(
-            memory_format=torch.channels_last if addend.dim() == 4 else torch.contiguous_format)
+        _check_addend(addend, out, addend_mask, a["Ncol"])
     act_id = (act if isinstance(act, int) else ACT[act]) if act is not None else (1 if relu else 0)
     if aux is not None:
         assert aux.dtype == torch.bfloat16 and aux.numel() == out.numel()
@@ -686,8 +530,7 @@ def conv_nt(src, b, out, *, stats=None, bias=None, relu=False, act=None, variant
         variant = select_nt_variant(src, b, out, with_stats=stats is not None, bias=bias, act=act_id, aux=aux,
                                     addend=addend, **a)
     if addend_mask is not None:
-        assert addend is not None and addend_mask.dtype == torch.uint8 and addend_mask.numel() * 8 == addend.numel()
-        assert a["ldo"] == a["Ncol"]
+        assert addend is not None and a["ldo"] == a["Ncol"]
     lib = _load()
     rc = lib.pdt_conv_nt(*_nt_args(src, b, out, stats, bias, a, act_id, variant, addend, aux, addend_mask))
     if rc == NOT_APPLICABLE:  # a cached variant tuned for another epilogue (e.g. the streaming 1x1 kernel)
@@ -736,29 +579,20 @@ def conv_wgrad_bn(dA, x, out, y, coef, run_ref, **a):
     lib = _load()
     assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.numel() == 5 * a["Mo"]
     assert y.dtype == torch.bfloat16 and y.shape == dA.shape
-    key = "wgb:" + ",".join(str(a[k]) for k in ("M", "Mo", "No", "Hs", "Ws", "C", "Hm", "Wm", "sh", "ntw")) + \
-        (f",p{a['pix']}" if a.get("pix") else "")
-    table = _tuned()
-    v = table.get(key)
-    if v is None:
-        if not _tune_allowed():
-            return False
 
-        def run(v):
-            return _wgrad_launch(lib, dA, x, out, v, 1.0, False, a, bna=(y, coef))
-        best = _time_variants(max(WGB_VARIANTS) + 1, run, set(WGB_VARIANTS))
-        if best >= 0 and _time_fn(run_ref) < _time_fn(lambda: run(best)):
-            best = AX_UNFUSED
-        table[key] = v = best
-        _save_tuned()
-    v = int(v)
-    if v < 0:
+    def run(v):
+        return _wgrad_launch(lib, dA, x, out, v, 1.0, False, a, bna=(y, coef))
+
+    v = autotune.choose(_wg_key(a, True), lambda: (WGB_VARIANTS, run), AX_UNFUSED, ref=run_ref)
+    if v < 0:  # (tuning not allowed and no entry: not taken, and nothing stored)
         return False
-    _chk(_wgrad_launch(lib, dA, x, out, v, 1.0, False, a, bna=(y, coef)), "conv_wgrad (BN backward apply)")
+    _chk(run(v), "conv_wgrad (BN backward apply)")
     return True
 
 
-_WG_KEYS: dict = {}
+def _wg_key(a, bn=False):
+    return autotune.wg_key(a["M"], a["Mo"], a["No"], a["Hs"], a["Ws"], a["C"], a["Hm"], a["Wm"], a["sh"], a["ntw"],
+                           a.get("pix", 0), bn)
 
 
 def conv_wgrad(dy, x, out, *, scale=1.0, accumulate=False, variant=None, bias_out=None, **a):
@@ -779,31 +613,10 @@ def conv_wgrad(dy, x, out, *, scale=1.0, accumulate=False, variant=None, bias_ou
     assert out.device == dy.device == x.device, "weight gradient operands on different devices"
     lib = _load()
     if variant is None:
-        gt = (a["M"], a["Mo"], a["No"], a["Hs"], a["Ws"], a["C"], a["Hm"], a["Wm"], a["sh"], a["ntw"], a.get("pix", 0))
-        key = _WG_KEYS.get(gt)
-        if key is None:
-            key = "wg2:" + ",".join(str(x) for x in gt[:10])
-            if a.get("pix"):
-                key += f",p{a['pix']}"
-            _WG_KEYS[gt] = key
-        table = _tuned()
-        spec = os.environ.get("PDT_RETUNE_WG")  # targeted re-tune of shipped keys against these ids
-        if key in table and spec and key not in _RETUNED and _tune_allowed():
-            _RETUNED.add(key)
-            allowed = _id_set(spec) | {int(table[key])}
-            table[key] = _time_variants(lib.pdt_wgrad_num_variants(),
-                                        lambda v: _wgrad_launch(lib, dy, x, out, v, scale, False, a), allowed)
-            _save_tuned()
-        if key in table:
-            variant = int(table[key])
-        elif not _tune_allowed():
-            variant = -1
-        else:
-            best = _time_variants(lib.pdt_wgrad_num_variants(),
-                                  lambda v: _wgrad_launch(lib, dy, x, out, v, scale, False, a))
-            table[key] = best
-            _save_tuned()
-            variant = best
+        variant = autotune.choose(
+            _wg_key(a), lambda: (range(lib.pdt_wgrad_num_variants()),
+                                 lambda v: _wgrad_launch(lib, dy, x, out, v, scale, False, a)),
+            -1, retune="PDT_RETUNE_WG")
     rc = _wgrad_launch(lib, dy, x, out, variant, scale, accumulate, a, bias_out)
     if rc == NOT_APPLICABLE:  # e.g. a tuned halo id for a geometry it does not cover: the heuristic tile
         rc = _wgrad_launch(lib, dy, x, out, -1, scale, accumulate, a, bias_out)
@@ -1107,7 +920,6 @@ def _conv_dgrad(dy, w32, N, H, W, Cin, Cout, g, addend=None, addend_mask=None, b
     return dx, _BnbPartials(part, R, u, _BnbPartials(part2, R, u2) if second else None)
 
 
-_NTB_KEYS: dict = {}
 _BNB_GENERIC_VARIANT = 17  # 64x128 LDS tile, direct store: every BN-backward epilogue configuration
 
 
@@ -1115,30 +927,24 @@ def _select_bnb_variant(launch, a, has_addend, has_mask, device, two=False):
     """Variant for a data gradient with the fused BN-backward epilogue: its own
     tuned-table key (the epilogue's extra loads / registers shift the best tile);
     ``two``: also a second unit's partials (key suffix ",2", timed with them)."""
-    gt = (a["Hs"], a["Ws"], a["Cs"], a["Nimg"], a["Hm"], a["Wm"], a["Ncol"], a["K"], a["sh"], a["sw"], a["nth"],
-          a["ntw"], a["osh"], int(has_addend), int(has_mask)) + ((2,) if two else ())
-    key = _NTB_KEYS.get(gt)
-    if key is None:
-        key = _NTB_KEYS[gt] = "ntb2:" + ",".join(str(x) for x in gt)
-    geom = ",".join(str(x) for x in gt[:13])
-    table = _tuned()
-    allowed = _retune_candidates(key, table)
-    if key in table and allowed is None:
-        return int(table[key])
-    lib = _load()
-    M = a["Nimg"] * a["Hm"] * a["Wm"]
-    if not _tune_allowed():  # the plain data gradient's tuned tile, else the heuristic
-        plain = f"nt5:{geom},0,0"
-        return int(table[plain]) if plain in table else lib.pdt_conv_nt_resolve_variant(-1, M, a["Ncol"], a["K"])
-    nvar = lib.pdt_conv_nt_num_variants()
-    rows = max(lib.pdt_conv_nt_bnb_rows(M, a["Ncol"], a["K"], v) for v in range(nvar))
-    part = torch.empty(2 * rows * a["Ncol"], dtype=torch.float32, device=device)
-    part2 = torch.empty_like(part) if two else None
-    table[key] = _time_variants(nvar, lambda v: launch(v, part, lib.pdt_conv_nt_bnb_rows(M, a["Ncol"], a["K"], v),
-                                                       part2),
-                                allowed if allowed is not None else _variant_filter())
-    _save_tuned()
-    return table[key]
+    geom = (a["Hs"], a["Ws"], a["Cs"], a["Nimg"], a["Hm"], a["Wm"], a["Ncol"], a["K"], a["sh"], a["sw"], a["nth"],
+            a["ntw"], a["osh"])
+    M, Ncol, K = a["Nimg"] * a["Hm"] * a["Wm"], a["Ncol"], a["K"]
+
+    def setup():
+        lib = _load()
+        ids = range(lib.pdt_conv_nt_num_variants())
+        rows = max(lib.pdt_conv_nt_bnb_rows(M, Ncol, K, v) for v in ids)
+        part = torch.empty(2 * rows * Ncol, dtype=torch.float32, device=device)
+        part2 = torch.empty_like(part) if two else None
+        return ids, lambda v: launch(v, part, lib.pdt_conv_nt_bnb_rows(M, Ncol, K, v), part2)
+
+    def default():  # the plain data gradient's tuned tile, else the heuristic
+        plain = _tuned().get(autotune.nt_key(*geom, 0, 0))
+        return int(plain) if plain is not None else _load().pdt_conv_nt_resolve_variant(-1, M, Ncol, K)
+
+    return autotune.choose(autotune.ntb_key(*geom, has_addend, has_mask, two), setup, default,
+                           retune="PDT_RETUNE_WITH", first_only="PDT_NT_VARIANTS")
 
 
 def _conv_wgrad(dy, x, N, H, W, Cs, Cout, g, out):
@@ -1386,24 +1192,6 @@ def _ax_launch(lib, src, b, out, v, a, stats=None, bnb=None, ax=None):
                               _s())
 
 
-def _time_fn(fn):
-    """Best of two 3-launch HIP-event trials after one warm call (``_time_variants``' protocol), ms."""
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fn()
-    best = float("inf")
-    for _ in range(2):
-        ev0.record()
-        for _ in range(3):
-            fn()
-        ev1.record()
-        ev1.synchronize()
-        best = min(best, ev0.elapsed_time(ev1))
-    return best
-
-
-AX_UNFUSED = -2  # tuned-table value: the element pass + the plain GEMM beat every AX tile here
-
-
 def _ax2_launch(lib, src, b, out, v, a, stats=None, bnb=None, ax=None, addend=None, addend_mask=None):
     """``_ax_launch`` for any stride-1 geometry (``a`` as ``_fwd_nt_geom`` / ``_conv_dgrad`` build it);
     ``addend`` (+ ``addend_mask``): added in the fused BN-backward epilogue (modes 2 / 3)."""
@@ -1423,23 +1211,8 @@ def _ax_select(key, run, run_ref=None):
     ``run_ref()``: the unfused alternative (element pass + the plain GEMM's tuned tile);
     when it is faster the key records ``AX_UNFUSED`` and the caller takes that path (the
     fold is a per-geometry tuning decision, not a blanket switch)."""
-    table = _tuned()
-    extra = os.environ.get("PDT_RETUNE_AX")  # targeted re-tune of shipped AX keys (as PDT_RETUNE_WITH)
-    if key in table and not (extra and key not in _RETUNED and _tune_allowed()):
-        return int(table[key])
-    if not _tune_allowed():
-        return AX_VARIANTS[3]  # 128x128, one LDS stage
-    cand = set(AX_VARIANTS)
-    if key in table:
-        _RETUNED.add(key)
-        cur = int(table[key])
-        cand = _id_set(extra) | ({cur} if cur >= 0 else set())
-    best = _time_variants(max(cand) + 1, run, cand)
-    if best >= 0 and run_ref is not None and _time_fn(run_ref) < _time_fn(lambda: run(best)):
-        best = AX_UNFUSED
-    table[key] = best
-    _save_tuned()
-    return best
+    return autotune.choose(key, lambda: (AX_VARIANTS, run), AX_VARIANTS[3],  # default: 128x128, one LDS stage
+                           retune="PDT_RETUNE_AX", ref=run_ref)
 
 
 def _conv3_dgrad_bn_bwd(dout, u3, k1, k2, k3, dy3, u2, side=None):
@@ -1492,8 +1265,7 @@ def _conv3_dgrad_bn_bwd(dout, u3, k1, k2, k3, dy3, u2, side=None):
             side_apply()
         return rc
 
-    key = ("axd:" if side is not None else "axb:") + ",".join(str(x) for x in (H, W, Cout, N, Cin))
-    v = _ax_select(key, run_tuned, run_ref)
+    v = _ax_select(autotune.axb_key(H, W, Cout, N, Cin, side is not None), run_tuned, run_ref)
     if v < 0:
         return None
     R = lib.pdt_conv_nt_bnb_rows(M, Cin, Cout, v)
@@ -1557,10 +1329,7 @@ def _conv_fwd_ax(pu: _Unit, xbuf, wb, N, H, W, Cs, Cout, g, with_stats):
         _apply_pending(pu)
         _conv_forward(xbuf, wb, N, H, W, Cs, Cout, g, with_stats=with_stats)
 
-    key = "axf:" + ",".join(str(x) for x in (H, W, Cs, N, Cout, int(res is not None), int(ru is not None),
-                                              int(with_stats)))
-    if g["KH"] != 1 or g["KW"] != 1:
-        key += f",k{g['KH']}x{g['KW']}p{g['ph']}"
+    key = autotune.axf_key(H, W, Cs, N, Cout, res is not None, ru is not None, with_stats, g["KH"], g["KW"], g["ph"])
     v = _ax_select(key, run, run_ref)
     if v < 0:
         return None
@@ -1614,9 +1383,8 @@ def _conv2_dgrad_bn_bwd(da2, u2, k1, k2, k3, dy2, u1, bnb_mask=None, addend=None
                                   _p(dy2), None, N * Ho * Wo, Cout, 1, None, _s()), "bn_bwd_apply")
         _unit_dx(dy2, u2, addend=addend, addend_mask=addend_mask, bnb_unit=u1, bnb_mask=bnb_mask)
 
-    key = "ax3:" + ",".join(str(x) for x in (Ho, Wo, Cout, N, Cin, KH, KW, ph))
-    if addend is not None or bnb_mask is not None:
-        key += f",a{int(addend is not None)}{int(addend_mask is not None)}m{int(bnb_mask is not None)}"
+    key = autotune.ax3_key(Ho, Wo, Cout, N, Cin, KH, KW, ph, addend is not None, addend_mask is not None,
+                           bnb_mask is not None)
     v = _ax_select(key, run, run_ref)
     if v < 0:
         return None
@@ -1988,25 +1756,14 @@ def _stem_halo_choice(x4, wb, y, N, H, W, Cout, a, v) -> bool:
     lib = _load()
     if os.environ.get("PDT_STEM_HALO", "1") == "0" or lib.pdt_stem_fwd_rows(N, H, W, Cout) < 0:
         return False
-    key = f"stem1:{N},{H},{W},{Cout}"
-    table = _tuned()
-    if key in table:
-        return int(table[key]) == 1
-    if not _tune_allowed():
-        return True
-    f32 = dict(dtype=torch.float32, device=x4.device)
-    Rh = lib.pdt_stem_fwd_rows(N, H, W, Cout)
-    ph = torch.empty(2 * Rh * Cout, **f32)
-    Rg = conv_stat_rows(N * H * W // 4, Cout, a["K"], v)
-    pg = torch.empty(2 * Rg * Cout, **f32)
 
-    def launch(k):
-        if k == 1:
-            return lib.pdt_stem_fwd(_p(x4), _p(wb), _p(y), _p(ph), N, H, W, Cout, _s())
-        return lib.pdt_conv_nt(*_nt_args(x4, wb, y, pg, None, a, 0, v))
-    table[key] = _time_variants(2, launch)
-    _save_tuned()
-    return int(table[key]) == 1
+    def setup():
+        rows = lib.pdt_stem_fwd_rows(N, H, W, Cout), conv_stat_rows(N * H * W // 4, Cout, a["K"], v)
+        ph, pg = (torch.empty(2 * r * Cout, dtype=torch.float32, device=x4.device) for r in rows)
+        return (0, 1), lambda k: lib.pdt_stem_fwd(_p(x4), _p(wb), _p(y), _p(ph), N, H, W, Cout, _s()) if k == 1 \
+            else lib.pdt_conv_nt(*_nt_args(x4, wb, y, pg, None, a, 0, v))
+
+    return autotune.choose(autotune.stem_key(N, H, W, Cout), setup, 1) == 1
 
 
 def _unit_fwd_s2d(x, w, gamma, beta, bna: _BNArgs):
@@ -2081,19 +1838,9 @@ def _stem_wgrad_halo(u: _Unit, dA, coef, dw256, generic) -> bool:
             rc = lib.pdt_wgrad_reduce(_p(ws[v]), _p(dw256), None, None, splits, Cout, 256, 1.0, 0, _s())
         return rc
 
-    key = f"stem2w:{N},{H},{W},{Cout}"
-    table = _tuned()
-    if key in table:
-        choice = int(table[key])
-    elif not _tune_allowed():
-        choice = 1
-    else:
-        choice = _time_variants(2, run_halo)
-        generic()  # settles the generic path's own tuning before it is timed
-        if choice < 0 or _time_fn(generic) < _time_fn(lambda: run_halo(choice)):
-            choice = -1
-        table[key] = choice
-        _save_tuned()
+    # (one untimed generic() settles the generic path's own tuning before it is timed)
+    choice = autotune.choose(autotune.stem_key(N, H, W, Cout, True), lambda: ((0, 1), run_halo), 1,
+                             ref=generic, ref_value=-1, ref_first=True)
     if choice < 0:
         return False
     _chk(run_halo(choice), "stem_wgrad")
@@ -2538,11 +2285,8 @@ def gemm_f8(a, b, out, dq_a, dq_b, *, fmt_a=E4M3, bias=None, act=0, aux=None, ad
                           _p(aux), _p(addend), v, _s())
         nv = lib.pdt_gemm_f8_num_variants()
         if variant is None:
-            # ",r": a residual addend in the epilogue (a different best tile); "f8c": the variant
-            # set with the dense ring (ids 12 / 13)
-            key = f"f8c:{M},{N},{K},{fmt_a},{act},{int(bias is not None)}" + (",r" if addend is not None and act == 0
-                                                                               else "")
-            variant = _autotune(key, nv, lambda v: lib.pdt_gemm_f8(*args(v)))
+            key = autotune.f8_key(M, N, K, fmt_a, act, bias is not None, addend is not None and act == 0)
+            variant = autotune.choose(key, lambda: (range(nv), lambda v: lib.pdt_gemm_f8(*args(v))), 0)
         if variant >= nv:
             variant = -1  # (a stale table entry: the built-in native choice)
         _chk_v(lib.pdt_gemm_f8(*args(variant)), "gemm_f8")
@@ -2554,16 +2298,13 @@ def gemm_f8(a, b, out, dq_a, dq_b, *, fmt_a=E4M3, bias=None, act=0, aux=None, ad
     args = lambda v: (_p(a), _p(b), _p(out), _p(bias), _p(dq_a), _p(dq_b), M, N, K, K, K, N, fmt_a, act,  # noqa
                       _p(aux), _p(addend), v, _p(codes), _p(meta), _p(part), int(qfmt), int(only), _p(dq), _s())
     if variant is None:
-        key = f"f8c:{M},{N},{K},{fmt_a},{act},{int(bias is not None)},q{qfmt}{int(only)}" + \
-            (",cs" if colsum_out is not None else "")
-        table = _tuned()
-        if key in table:
-            variant = int(table[key])
-        else:
-            # (tuning launches roll the history too: tune on a scratch copy of the state)
+        def setup():  # (tuning launches roll the history too: tune on a scratch copy of the state)
             scratch = meta.clone()
             targs = lambda v: args(v)[:17] + (_p(codes), _p(scratch)) + args(v)[19:]  # noqa: E731
-            variant = _autotune(key, lib.pdt_gemm_f8_num_variants(), lambda v: lib.pdt_gemm_f8_q8(*targs(v)))
+            return range(lib.pdt_gemm_f8_num_variants()), lambda v: lib.pdt_gemm_f8_q8(*targs(v))
+
+        variant = autotune.choose(autotune.f8_key(M, N, K, fmt_a, act, bias is not None, False, (int(qfmt), int(only)),
+                                                  colsum_out is not None), setup, 0)
     if colsum_out is not None:
         assert colsum_out.dtype == torch.float32 and colsum_out.numel() == N and colsum_out.is_contiguous()
         if variant == 7 or variant < 0:  # the direct-store tile has no staged epilogue
@@ -2604,18 +2345,10 @@ def linear_wgrad_f8(dyq, xq, dq_dy, dq_x, dy16=None, with_bias=False, variant=No
     db = (_grad_buf(b, (Nout,)) if b is not None else torch.empty(Nout, dtype=torch.float32, device=dyq.device)) \
         if with_bias else None
     if variant is None:
-        key = f"wg8:{M},{Nout},{K}"
-        table = _tuned()
-        if key in table:
-            variant = int(table[key])
-        elif not _tune_allowed():
-            variant = 0
-        else:
-            best = _time_variants(lib.pdt_wgrad_f8_num_variants(),
-                                  lambda v: _wgrad_f8_launch(lib, dyq, xq, dq_dy, dq_x, None, dw, None, v) or 0)
-            table[key] = best
-            _save_tuned()
-            variant = best
+        variant = autotune.choose(
+            autotune.wg8_key(M, Nout, K),
+            lambda: (range(lib.pdt_wgrad_f8_num_variants()),
+                     lambda v: _wgrad_f8_launch(lib, dyq, xq, dq_dy, dq_x, None, dw, None, v)), 0)
     _wgrad_f8_launch(lib, dyq, xq, dq_dy, dq_x, dy16 if with_bias else None, dw, db, variant)
     return dw, db
 

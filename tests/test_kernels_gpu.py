@@ -779,3 +779,56 @@ def test_fused_sgd_unaligned_and_aligned_chunks_match_torch():
             b.step()
         for p, q in zip(ps, ref):
             assert torch.allclose(p, q, rtol=1e-6, atol=1e-6), off
+
+
+def test_first_use_tunes_stores_and_then_only_looks_up(monkeypatch, tmp_path):
+    """conv_nt and conv_wgrad on an untuned 1x1 geometry (2 x 8x8 x 64 -> 64): the first call of each
+    times its variants and writes its key to the cache file; the second call times nothing."""
+    import json
+    from pytorch_distributed_template_amd.ops import autotune
+    monkeypatch.setenv("PDT_AUTOTUNE_SHIPPED", "0")
+    monkeypatch.setenv("PDT_TUNE_ROUNDS", "1")
+    for var in ("PDT_AUTOTUNE", "PDT_DETERMINISTIC", "WORLD_SIZE", "RANK", "PDT_NT_VARIANTS", "PDT_RETUNE_WITH",
+                "PDT_RETUNE_WG"):
+        monkeypatch.delenv(var, raising=False)
+    cache = tmp_path / "tune.json"
+    monkeypatch.setattr(autotune, "CACHE_PATH", cache)
+    monkeypatch.setattr(autotune, "_table", None)
+    monkeypatch.setattr(autotune, "_frozen", False)
+    trials, real = [], autotune.trial_ms
+    monkeypatch.setattr(autotune, "trial_ms", lambda fn: (trials.append(1), real(fn))[1])
+
+    torch.manual_seed(0)
+    N, C, H, W, Cout = 2, 64, 8, 8, 64
+    conv = nn.Conv2d(C, Cout, 1, bias=False).to("cuda")
+    x = _cl(torch.randn(N, C, H, W, device="cuda").to(torch.bfloat16))
+    dy = _cl(torch.randn(N, Cout, H, W, device="cuda").to(torch.bfloat16))
+    g = no._fwd_geom(N, H, W, C, conv)
+    a = no._fwd_nt_geom(N, H, W, C, Cout, g)
+    wa = dict(M=N * H * W, Mo=Cout, No=C, ldy=Cout, Hs=H, Ws=W, C=C, Hm=H, Wm=W, sh=1, sw=1, oh0=0, ow0=0, dh=1, dw=1,
+              ntw=1)
+    wb = no.bf16_weight(conv.weight)
+    wr = conv.weight.detach().to(torch.bfloat16).float()
+    ref = F.conv2d(x.float(), wr)
+    rdw = torch.nn.grad.conv2d_weight(x.float(), wr.shape, dy.float())
+
+    def run():
+        y = torch.empty_like(dy)
+        dw = torch.empty((Cout, C, 1, 1), device="cuda", memory_format=torch.channels_last)
+        no.conv_nt(x, wb, y, **a)
+        no.conv_wgrad(dy, x, dw, **wa)
+        return y, dw
+
+    y, dw = run()
+    assert relerr(y, ref) < 1e-2 and relerr(dw, rdw) < 1e-2
+    k_nt = autotune.nt_key(H, W, C, N, H, W, Cout, C, 1, 1, 1, 1, 1, False, False)
+    k_wg = autotune.wg_key(N * H * W, Cout, C, H, W, C, H, W, 1, 1)
+    stored = json.loads(cache.read_text())
+    assert set(stored) == {k_nt, k_wg} == set(autotune.tuned())
+    assert 0 <= stored[k_nt] < no._load().pdt_conv_nt_num_variants()
+    assert 0 <= stored[k_wg] < no._load().pdt_wgrad_num_variants()
+    timed = len(trials)
+    assert timed >= 2
+    y2, dw2 = run()
+    assert len(trials) == timed and json.loads(cache.read_text()) == stored
+    assert relerr(y2, ref) < 1e-2 and relerr(dw2, rdw) < 1e-2
