@@ -900,9 +900,6 @@ PDT_API int pdt_attn_fwd(const void* qkv, void* out, float* lse, int B, int T, i
   PDT_RETURN_LAUNCH();
 }
 
-PDT_API int pdt_fp8_meta_roll_partial(float* meta, const float* partial, int nblk, int fmt, float* dq_out,
-                                      hipStream_t st);
-
 static int attn_bwd_impl(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                          void* dqkv, int B, int T, int H, float scale, void* q8, float* q8_meta, float* q8_part,
                          float* q8_dq, hipStream_t st);

@@ -451,12 +451,6 @@ __global__ void __launch_bounds__(512) attn_bwd_f8_kernel(AttnBwdF8Params p) {
 static int attn_bwd_f8(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B,
                        int T, int H, float scale, float* dbg, const AttnBwdF8Params* q8, hipStream_t st);
 
-PDT_API int pdt_fp8_meta_roll_partial(float* meta, const float* partial, int nblk, int fmt, float* dq_out,
-                                      hipStream_t st);
-PDT_API long pdt_reduce_rows_work(int nrows, int n);
-PDT_API int pdt_wgrad_reduce_rows(const float* rows, float* out, int nrows, int n, float scale, int accumulate,
-                                  float* work, hipStream_t st);
-
 // Workgroups of the backward launch: the length of the q8_part the caller passes to
 // pdt_attn_bwd_f8_q8.
 static int attn_bwd_grid(int nbh);

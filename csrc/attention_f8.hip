@@ -505,9 +505,6 @@ PDT_API int pdt_attn_fwd_f8(const void* qkv, void* out, float* lse, int B, int T
   PDT_RETURN_LAUNCH();
 }
 
-PDT_API int pdt_fp8_meta_roll_partial(float* meta, const float* partial, int nblk, int fmt, float* dq_out,
-                                      hipStream_t st);
-
 // pdt_attn_fwd_f8 that also writes the e4m3 codes of O for the projection GEMM (delayed scale
 // q8_meta[0]), rolls that GEMM's amax history (q8_part: B*H floats) and writes the codes'
 // dequant factor to q8_dq

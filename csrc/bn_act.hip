@@ -4,8 +4,8 @@
 // backward  relu-bwd -> add-bwd -> BN-bwd(dscale/dbias, dx)  (SURVEY §2.6(b):
 // these memory-bound passes cost about as much as the convs at 8 TB/s).
 //
-// Forward : y (conv output) -> per-channel partial (sum, sumsq)   [bn_stats]
-//           (or taken from the conv epilogue)  -> finalize         [bn_finalize]
+// Forward : per-channel partial (sum, sumsq) of y (conv output), written by
+//           the conv epilogue                  -> finalize         [bn_finalize]
 //           a = act(y * scale + shift (+ res))  one read, one write [bn_apply]
 // Backward: dz = dA * relu'(.)  ; partial (sum dz, sum dz*(y-mean)) [bn_bwd_reduce]
 //           -> dgamma, dbeta, and dy = k1*dz + k2*y + k3            [bn_bwd_finalize]
@@ -37,53 +37,6 @@ __device__ __forceinline__ void load8f(const float* p, float* f) {
   f32x4 b = *reinterpret_cast<const f32x4*>(p + 4);
   f[0] = a[0]; f[1] = a[1]; f[2] = a[2]; f[3] = a[3];
   f[4] = b[0]; f[5] = b[1]; f[6] = b[2]; f[7] = b[3];
-}
-
-// -------------------------------------------------------------------- stats
-// grid: G blocks; block b handles rows b, b+G, ... in passes of RP rows.
-__global__ void __launch_bounds__(NT) bn_stats_kernel(const u16* __restrict__ y, float* __restrict__ part, long M,
-                                                      int C) {
-  __shared__ float red[2][NT][8];
-  const int cpr = C / 8;               // chunks per row
-  const int rp = NT / cpr;             // rows per pass
-  const int t = threadIdx.x;
-  const int ch = t % cpr, rr = t / cpr;
-  float s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (rr < rp) {
-    for (long r = (long)blockIdx.x * rp + rr; r < M; r += (long)gridDim.x * rp) {
-      u32x4 v = *reinterpret_cast<const u32x4*>(y + r * C + ch * 8);
-      float f[8];
-      unpack8(v, f);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        s[k] += f[k];
-        q[k] += f[k] * f[k];
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    red[0][t][k] = s[k];
-    red[1][t][k] = q[k];
-  }
-  __syncthreads();
-  // reduce over rr for each ch
-  if (t < cpr) {
-    float as[8] = {0, 0, 0, 0, 0, 0, 0, 0}, aq[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int j = 0; j < rp; ++j) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        as[k] += red[0][j * cpr + t][k];
-        aq[k] += red[1][j * cpr + t][k];
-      }
-    }
-    const long R = gridDim.x;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      part[(long)blockIdx.x * C + t * 8 + k] = as[k];
-      part[(R + blockIdx.x) * C + t * 8 + k] = aq[k];
-    }
-  }
 }
 
 // Parallel first stage of the partial-row reduction: [2][R][C] -> [2][G][C].
@@ -510,8 +463,8 @@ __global__ void __launch_bounds__(NT) bn_bwd_apply_kernel(const u16* __restrict_
   }
 }
 
-// elementwise trip unroll of bn_apply / bn_bwd_apply (PDT_BN_UNROLL=1|2|4, default 1;
-// pdt_bn_set_unroll for in-process A/B runs). Measured at ResNet-50 stage 1, bs 1024
+// elementwise trip unroll of bn_apply / bn_bwd_apply (PDT_BN_UNROLL=1|2|4, default 1; 11:
+// unroll 1 + nontemporal stores). Measured at ResNet-50 stage 1, bs 1024
 // (scripts/bench_bn.py, one MI355X): apply 4.49 / 4.38 / 4.45 TB/s and backward apply
 // 4.91 / 4.47 / 4.44 TB/s for U = 1 / 2 / 4 -- the grid-stride loop already keeps
 // enough bytes in flight; deeper trips only cost occupancy.
@@ -541,12 +494,6 @@ int grid_for(long n8, int C) {
 
 }  // namespace
 
-PDT_API int pdt_bn_set_unroll(int u) {  // 1 / 2 / 4: trip unroll; 11: unroll 1 + nontemporal stores
-  if (u != 1 && u != 2 && u != 4 && u != 11) return -1;
-  g_bn_unroll = u;
-  return 0;
-}
-
 PDT_API int pdt_bn_stats_blocks(long M, int C) {
   int cpr = C / 8;
   int rp = NT / cpr;
@@ -561,12 +508,6 @@ PDT_API int pdt_bn_stats_blocks(long M, int C) {
   if (b > cap) b = cap;
   if (b < 1) b = 1;
   return (int)b;
-}
-
-PDT_API int pdt_bn_stats(const void* y, float* part, long M, int C, int blocks, hipStream_t st) {
-  if (C % 8 || C / 8 > NT) return -1;
-  hipLaunchKernelGGL(bn_stats_kernel, dim3(blocks), dim3(NT), 0, st, (const u16*)y, part, M, C);
-  PDT_RETURN_LAUNCH();
 }
 
 // Number of floats of extra workspace the finalize calls need after the

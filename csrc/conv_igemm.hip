@@ -519,21 +519,6 @@ PDT_API int pdt_conv_nt_ax3(const void* src, const void* b, void* out, float* st
                       stream, ax);
 }
 
-PDT_API int pdt_conv_nt_ax2(const void* src, const void* b, void* out, float* stats,
-                            int Hs, int Ws, int Cs, int Nimg, int Hm, int Wm, int Ncol, int K, int ldb,
-                            int sh, int sw, int oh0, int ow0, int dh, int dw, int nth, int ntw,
-                            int Ho, int Wo, int osh, int osw, int oph, int opw, int ldo, int variant,
-                            const void* bn_y, const float* bn_mean, const float* bn_scale, const float* bn_shift,
-                            const void* bn_mask, float* part, int relu, int row0, int R,
-                            int ax_mode, const void* ax_y2, const float* ax_c1, const float* ax_c2,
-                            const float* ax_c3, const float* ax_rsc, const float* ax_rsh, const void* ax_mask_in,
-                            void* ax_mask_out, void* ax_dst, hipStream_t stream) {
-  return pdt_conv_nt_ax3(src, b, out, stats, nullptr, nullptr, Hs, Ws, Cs, Nimg, Hm, Wm, Ncol, K, ldb, sh, sw, oh0,
-                         ow0, dh, dw, nth, ntw, Ho, Wo, osh, osw, oph, opw, ldo, variant, bn_y, bn_mean, bn_scale,
-                         bn_shift, bn_mask, part, relu, row0, R, ax_mode, ax_y2, ax_c1, ax_c2, ax_c3, ax_rsc, ax_rsh,
-                         ax_mask_in, ax_mask_out, ax_dst, stream);
-}
-
 // the 1x1 form (stride 1, unpadded)
 PDT_API int pdt_conv_nt_ax(const void* src, const void* b, void* out, float* stats,
                            int Hs, int Ws, int Cs, int Nimg, int Hm, int Wm, int Ncol, int K, int ldb,
@@ -543,9 +528,10 @@ PDT_API int pdt_conv_nt_ax(const void* src, const void* b, void* out, float* sta
                            int ax_mode, const void* ax_y2, const float* ax_c1, const float* ax_c2,
                            const float* ax_c3, const float* ax_rsc, const float* ax_rsh, const void* ax_mask_in,
                            void* ax_mask_out, void* ax_dst, hipStream_t stream) {
-  return pdt_conv_nt_ax2(src, b, out, stats, Hs, Ws, Cs, Nimg, Hm, Wm, Ncol, K, ldb, 1, 1, 0, 0, 1, 1, 1, 1, Hm, Wm,
-                         1, 1, 0, 0, ldo, variant, bn_y, bn_mean, bn_scale, bn_shift, bn_mask, part, relu, row0, R,
-                         ax_mode, ax_y2, ax_c1, ax_c2, ax_c3, ax_rsc, ax_rsh, ax_mask_in, ax_mask_out, ax_dst, stream);
+  return pdt_conv_nt_ax3(src, b, out, stats, nullptr, nullptr, Hs, Ws, Cs, Nimg, Hm, Wm, Ncol, K, ldb, 1, 1, 0, 0, 1,
+                         1, 1, 1, Hm, Wm, 1, 1, 0, 0, ldo, variant, bn_y, bn_mean, bn_scale, bn_shift, bn_mask, part,
+                         relu, row0, R, ax_mode, ax_y2, ax_c1, ax_c2, ax_c3, ax_rsc, ax_rsh, ax_mask_in, ax_mask_out,
+                         ax_dst, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -554,9 +540,6 @@ PDT_API int pdt_conv_nt_ax(const void* src, const void* b, void* out, float* sta
 // optional bf16 addend [M][ldo] (residual add, or the GELU-backward operand with act 3 / the
 // stored GELU derivative with act 5); act 4 = GELU with its derivative written to aux.
 // K, lda, ldb in BYTES (= elements), multiples of 128 / 16 / 16.
-PDT_API int pdt_fp8_meta_roll_partial(float* meta, const float* partial, int nblk, int fmt, float* dq_out,
-                                      hipStream_t st);
-
 namespace {
 // id 11: the 256x256 tile on FOUR waves (2x2 of 128x128, 256 accumulators per lane, one wave
 // per SIMD): per K-tile a CU's fragment reads fall from 192 KB (8 waves of 128x64) to 128 KB
@@ -591,19 +574,6 @@ int launch_f8(int v, const NTParams& p, hipStream_t st) {
 }  // namespace
 
 PDT_API int pdt_gemm_f8_num_variants() { return NVAR_F8; }
-
-PDT_API int pdt_gemm_ring(const void* a, const void* b, void* c, const float* bias, const float* dq_a,
-                          const float* dq_b, int M, int N, int K, int lda, int ldb, int ldc, int dt, int sub,
-                          hipStream_t st);
-PDT_API int pdt_gemm_ring_epi(const void* a, const void* b, void* c, const float* bias, const float* dq_a,
-                              const float* dq_b, int M, int N, int K, int lda, int ldb, int ldc, int dt, int act,
-                              void* aux, const void* addend, void* q8, const float* q8_meta, float* q8_part,
-                              int q8_fmt, int q8_only, float* colsum, hipStream_t st);
-PDT_API int pdt_gemm_ring_epi_pers(const void* a, const void* b, void* c, const float* bias, const float* dq_a,
-                                   const float* dq_b, int M, int N, int K, int lda, int ldb, int ldc, int dt, int act,
-                                   void* aux, const void* addend, void* q8, const float* q8_meta, float* q8_part,
-                                   int q8_fmt, int q8_only, float* colsum, hipStream_t st);
-PDT_API int pdt_gemm_ring_grid(int M, int N, int sub);
 
 static int gemm_f8_impl(const void* a, const void* b, void* out, const float* bias, const float* dq_a,
                         const float* dq_b, int M, int N, int K, int lda, int ldb, int ldo, int fmt_a, int act,

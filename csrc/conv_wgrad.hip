@@ -437,11 +437,6 @@ static WGVar wg_variant(int v, int Mo, int No) {
 constexpr int WG_RING = WG_NVAR + 1;
 PDT_API int pdt_wgrad_num_variants() { return WG_NVAR + 2; }
 PDT_API int pdt_wgrad_halo_id() { return WG_NVAR; }
-PDT_API int pdt_wgrad_ring_id() { return WG_RING; }
-PDT_API int pdt_wgrad_ring_ok(int Mo, int No, int C, int pix);
-PDT_API int pdt_wgrad_ring_launch(const void* dy, const void* x, float* slab, int M, int Mo, int No, int ldy,
-                                  int Hs, int Ws, int C, int Hm, int Wm, int sh, int sw, int oh0, int ow0, int dh,
-                                  int dw, int ntw, int splits, int ktiles_per_split, int pix, hipStream_t st);
 
 // the ring's split plan: one workgroup per CU, so the dispatch-wave model -- splits s <= the
 // k-tiles / 8 minimising (waves of tiles*s over the CUs) x (k-tiles per split)
@@ -585,7 +580,7 @@ static long wg_slots(int v, const WGVar& w) {
 // multi-workgroup-per-CU tiles it picked grids of ~512 workgroups where ~2048 cycling through
 // the resident slots hide latency better (ResNet-50: 290-650 vs 262-582 us per call,
 // gpurun_out r4t vs r4w), so it is off by default here.
-PDT_API int pdt_wgrad_plan(int M, int Mo, int No, int variant, int* ktiles_per_split) {
+static int wgrad_plan(int M, int Mo, int No, int variant, int* ktiles_per_split) {
   const WGVar w = wg_variant(variant, Mo, No);
   const int BM = w.BM, BN = w.BN, target = w.target;
   int tiles = ((Mo + BM - 1) / BM) * ((No + BN - 1) / BN);
@@ -635,7 +630,7 @@ PDT_API int pdt_wgrad_plan2(int M, int Mo, int No, int Hs, int Ws, int C, int va
     if (pdt_wgrad_ring_ok(Mo, No, C, 0) != 0) return -5;
     return wgrad_ring_plan(M, Mo, No, per_split);
   }
-  return pdt_wgrad_plan(M, Mo, No, variant, per_split);
+  return wgrad_plan(M, Mo, No, variant, per_split);
 }
 
 // stage-1 slab groups of the reduction: enough (column-block x group) blocks to stream the slabs
@@ -648,32 +643,16 @@ static int reduce_groups(int splits, int Mo, int No) {
   return G;
 }
 
-// floats of workspace pdt_conv_wgrad needs for `splits` slabs: slabs + stage-1
+// floats of workspace pdt_conv_wgrad2 needs for `splits` slabs: slabs + stage-1
 // partials + the [splits][Mo] bias-gradient slab
 PDT_API long pdt_wgrad_workspace(int splits, int Mo, int No) {
   const long G = reduce_groups(splits, Mo, No);
   return (long)splits * Mo * No + (G > 1 ? G * Mo * No : 0) + (long)splits * Mo;
 }
 
-PDT_API int pdt_wgrad_reduce(float* slab, float* out, const float* bslab, float* bias_out, int splits, int Mo, int No,
-                             float scale, int accumulate, hipStream_t stream);
-
-// pdt_conv_wgrad2: the same with an optional BatchNorm backward apply on the dY operand
-// (WGParams.bn_y / bn_c: `dy` is then dA); variants 0..11 only (NOT_APPLICABLE otherwise).
-PDT_API int pdt_conv_wgrad2(const void* dy, const void* x, float* slab, float* out, int M, int Mo, int No,
-                            int ldy, int Hs, int Ws, int C, int Hm, int Wm, int sh, int sw, int oh0, int ow0,
-                            int dh, int dw, int ntw, int splits, int ktiles_per_split, float scale,
-                            int accumulate, int variant, int pix, float* bias_out, const void* bn_y,
-                            const float* bn_c, hipStream_t stream);
-
-PDT_API int pdt_conv_wgrad(const void* dy, const void* x, float* slab, float* out, int M, int Mo, int No,
-                           int ldy, int Hs, int Ws, int C, int Hm, int Wm, int sh, int sw, int oh0, int ow0,
-                           int dh, int dw, int ntw, int splits, int ktiles_per_split, float scale,
-                           int accumulate, int variant, int pix, float* bias_out, hipStream_t stream) {
-  return pdt_conv_wgrad2(dy, x, slab, out, M, Mo, No, ldy, Hs, Ws, C, Hm, Wm, sh, sw, oh0, ow0, dh, dw, ntw, splits,
-                         ktiles_per_split, scale, accumulate, variant, pix, bias_out, nullptr, nullptr, stream);
-}
-
+// Weight gradient by split-K slabs, reduced into out (= or += scale * sum), with an optional
+// BatchNorm backward apply on the dY operand (WGParams.bn_y / bn_c: `dy` is then dA; variants
+// 0..11 only, NOT_APPLICABLE otherwise).
 PDT_API int pdt_conv_wgrad2(const void* dy, const void* x, float* slab, float* out, int M, int Mo, int No,
                             int ldy, int Hs, int Ws, int C, int Hm, int Wm, int sh, int sw, int oh0, int ow0,
                             int dh, int dw, int ntw, int splits, int ktiles_per_split, float scale,

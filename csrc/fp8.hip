@@ -433,14 +433,6 @@ PDT_API int pdt_cast_fp8(const void* x, int bf16, long n, const float* partial, 
   PDT_RETURN_LAUNCH();
 }
 
-// fp32 [R][C] -> e4m3 [C][R]; the partials must come from pdt_amax_partial over the same R*C values
-PDT_API int pdt_cast_fp8_t(const float* x, int R, int C, const float* partial, void* q, hipStream_t st) {
-  const int nb = nblocks((long)R * C);
-  dim3 grid((C + 63) / 64, (R + 63) / 64);
-  hipLaunchKernelGGL(cast_fp8_t_kernel<0>, grid, dim3(256), 0, st, x, R, C, partial, nb, (uint8_t*)q);
-  PDT_RETURN_LAUNCH();
-}
-
 // fp32 [R][C] -> e4m3 [R][C] AND [C][R] in one pass (the weight's forward and data-gradient
 // operands), dq = 1 / scale; the partials must come from pdt_amax_partial over the same values
 PDT_API int pdt_cast_fp8_dual(const float* x, int R, int C, const float* partial, void* q, void* qt, float* dq,
@@ -487,10 +479,6 @@ PDT_API int pdt_gelu_dual_cast_fp8(const void* y, long n, float* meta, int fmt, 
   }
   PDT_RETURN_LAUNCH();
 }
-
-PDT_API int pdt_wgrad_reduce_rows(const float* rows, float* out, int nrows, int n, float scale, int accumulate,
-                                  float* work, hipStream_t stream);
-PDT_API long pdt_reduce_rows_work(int nrows, int n);
 
 // block shape of the column-summing casts: one thread per 8-column chunk, times up to 8 row groups
 // (PDT_CAST_CS_RG=1: the previous one-row-walker-per-chunk shape, for A/B runs)

@@ -371,9 +371,6 @@ PDT_API int pdt_ln_fwd(const void* x, const float* g, const float* b, void* y, f
   PDT_RETURN_LAUNCH();
 }
 
-PDT_API int pdt_fp8_meta_roll_partial(float* meta, const float* partial, int nblk, int fmt, float* dq_out,
-                                      hipStream_t st);
-
 PDT_API int pdt_ln_fwd_f8_blocks(int rows) { return (rows + WPB - 1) / WPB; }
 
 // LayerNorm of xsum = bf16(x + r) (written to xsum): the residual add of a pre-norm block moved
@@ -508,10 +505,6 @@ PDT_API int pdt_ln_bwd_f8(const void* dy, const void* x, const float* g, const f
                      accumulate);
   return pdt_fp8_meta_roll_partial(q8_meta, q8_part, blocks, 1, q8_dq, st);
 }
-
-PDT_API int pdt_wgrad_reduce_rows(const float* rows, float* out, int nrows, int n, float scale, int accumulate,
-                                  float* work, hipStream_t stream);
-PDT_API long pdt_reduce_rows_work(int nrows, int n);
 
 // pdt_ln_bwd_f8 + the column sums of dx (bf16 as stored) into bias_out [D] (= or += with
 // bias_acc): the bias gradient of the fp8 layer that produced the LayerNorm's input, so its

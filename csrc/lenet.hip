@@ -369,11 +369,12 @@ PDT_API int pdt_lenet_grad_row(int nc) { return grad_row(nc); }
 
 PDT_API int pdt_lenet_fwd(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
                           const float* wf1, const float* bf1, const float* wf2, const float* bf2, int B, int NC,
-                          int training, float p2, float p1, unsigned seed, float* logp, uint8_t* mask2,
-                          uint8_t* mask1, hipStream_t st) {
+                          int training, float p2, float p1, unsigned seed, float* logp, void* mask2, void* mask1,
+                          hipStream_t st) {
   LeNetArgs a{x, w1, b1, w2, b2, wf1, bf1, wf2, bf2, B, NC, training, p2, p1, seed};
   if (bad_args(a)) return -1;
-  hipLaunchKernelGGL(lenet_fwd_kernel, dim3(B), dim3(NT), 0, st, a, logp, mask2, mask1);
+  hipLaunchKernelGGL(lenet_fwd_kernel, dim3(B), dim3(NT), 0, st, a, logp, (uint8_t*)mask2,
+                     (uint8_t*)mask1);
   PDT_RETURN_LAUNCH();
 }
 

@@ -129,17 +129,6 @@ __global__ void transpose_cast_kernel(const float* __restrict__ w, u16* __restri
   }
 }
 
-// y = a + b (bf16, n % 8 == 0)
-__global__ void add_bf16_kernel(const u16* __restrict__ a, const u16* __restrict__ b, u16* __restrict__ y, long n8) {
-  for (long i = (long)blockIdx.x * NT + threadIdx.x; i < n8; i += (long)gridDim.x * NT) {
-    u32x4 va = reinterpret_cast<const u32x4*>(a)[i], vb = reinterpret_cast<const u32x4*>(b)[i];
-    u32x4 o;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = pack2bf(lo_bf(va[k]) + lo_bf(vb[k]), hi_bf(va[k]) + hi_bf(vb[k]));
-    reinterpret_cast<u32x4*>(y)[i] = o;
-  }
-}
-
 int grid_for(long n) {
   long b = (n + NT - 1) / NT;
   return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
@@ -191,13 +180,6 @@ PDT_API int pdt_wt_dgrad_multi(const void* jobs, int njobs, long total, hipStrea
 PDT_API int pdt_transpose_cast(const float* w, void* out, int R, int C, hipStream_t st) {
   dim3 g((C + 31) / 32, (R + 31) / 32);
   hipLaunchKernelGGL(transpose_cast_kernel, g, dim3(256), 0, st, w, (u16*)out, R, C);
-  PDT_RETURN_LAUNCH();
-}
-
-PDT_API int pdt_add_bf16(const void* a, const void* b, void* y, long n, hipStream_t st) {
-  if (n % 8) return -1;
-  hipLaunchKernelGGL(add_bf16_kernel, dim3(grid_for(n / 8)), dim3(NT), 0, st, (const u16*)a, (const u16*)b, (u16*)y,
-                     n / 8);
   PDT_RETURN_LAUNCH();
 }
 

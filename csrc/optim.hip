@@ -151,13 +151,6 @@ PDT_API int pdt_sgd_step2(const void* chunks, int nchunks, void* params, const v
   PDT_RETURN_LAUNCH();
 }
 
-PDT_API int pdt_sgd_step(const void* chunks, int nchunks, void* params, const void* grads, void* bufs, void* shadows,
-                         float lr, float momentum, float dampening, float wd, int nesterov, int first,
-                         float grad_scale, hipStream_t st) {
-  return pdt_sgd_step2(chunks, nchunks, params, grads, bufs, shadows, lr, momentum, dampening, wd, nesterov, first,
-                       grad_scale, nullptr, st);
-}
-
 PDT_API int pdt_adam_step2(const void* chunks, int nchunks, void* params, const void* grads, void* exp_avg,
                            void* exp_avg_sq, void* max_sq, void* shadows, float lr, float b1, float b2, float eps,
                            float wd, int decoupled, float bc1, float bc2, float grad_scale, float* dev, int tick,
@@ -173,11 +166,4 @@ PDT_API int pdt_adam_step2(const void* chunks, int nchunks, void* params, const 
                      (float* const*)exp_avg_sq, (float* const*)max_sq, (u16* const*)shadows, lr, b1, b2, eps, wd,
                      decoupled, bc1, bc2, grad_scale, (const float*)dev);
   PDT_RETURN_LAUNCH();
-}
-
-PDT_API int pdt_adam_step(const void* chunks, int nchunks, void* params, const void* grads, void* exp_avg,
-                          void* exp_avg_sq, void* max_sq, void* shadows, float lr, float b1, float b2, float eps,
-                          float wd, int decoupled, float bc1, float bc2, float grad_scale, hipStream_t st) {
-  return pdt_adam_step2(chunks, nchunks, params, grads, exp_avg, exp_avg_sq, max_sq, shadows, lr, b1, b2, eps, wd,
-                        decoupled, bc1, bc2, grad_scale, nullptr, 0, st);
 }

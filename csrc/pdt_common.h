@@ -1,11 +1,13 @@
 // Common definitions for the MI355X (gfx950 / CDNA4) kernel library.
 //
 // All kernels are plain HIP C++ written for wave64 + MFMA; the library exposes
-// a C ABI (PDT_API) that the Python layer calls through ctypes with raw device
-// pointers and the current HIP stream (no torch headers, no hipify).
+// a C ABI (PDT_API, declared once in pdt_api.h) that the Python layer calls through
+// ctypes with raw device pointers and the current HIP stream (no torch headers, no hipify).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "pdt_api.h"
 
 typedef unsigned short u16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -85,7 +87,6 @@ __device__ __forceinline__ uint32_t pdt_cvt4_f8(float a, float b, float c, float
   return (uint32_t)r;
 }
 
-#define PDT_API extern "C" __attribute__((visibility("default")))
 #define LDS_PTR(T) T __attribute__((address_space(3)))*
 
 __device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float(((uint32_t)v) << 16); }

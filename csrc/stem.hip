@@ -569,7 +569,6 @@ PDT_API int pdt_stem_wgrad_splits_v(int N, int H, int W, int Cout, int variant) 
 }
 
 // Slab rows (splits) of the halo stem weight gradient; -5 when the geometry is not covered.
-PDT_API int pdt_stem_wgrad_splits(int N, int H, int W, int Cout) { return pdt_stem_wgrad_splits_v(N, H, W, Cout, 0); }
 static int pdt_stem_wgrad_splits_v1(int N, int H, int W, int Cout) {
   if (Cout != 64 || H % (2 * WB) != 0 || W != 2 * WO || N < 1) return -5;
   const int ntiles = N * (H / 2 / WB);
@@ -579,14 +578,6 @@ static int pdt_stem_wgrad_splits_v1(int N, int H, int W, int Cout) {
 // slab[splits][64][256] = per-wave partials of the stem weight gradient (space-to-depth layout)
 // with the BN backward apply formed from dA, y and bnc = [k1; k2; k3; scale; shift] ([5][64]);
 // reduce with pdt_wgrad_reduce(slab, out, nullptr, nullptr, splits, 64, 256, ...).
-PDT_API int pdt_stem_wgrad_v(const void* x4, const void* dA, const void* y, const float* bnc, float* slab, int N,
-                             int H, int W, int Cout, int variant, hipStream_t stream);
-
-PDT_API int pdt_stem_wgrad(const void* x4, const void* dA, const void* y, const float* bnc, float* slab, int N, int H,
-                           int W, int Cout, hipStream_t stream) {
-  return pdt_stem_wgrad_v(x4, dA, y, bnc, slab, N, H, W, Cout, 0, stream);
-}
-
 // variant 0: v1 (register prefetch, 4-row bands), 1: v2 (all-DMA double-buffered, 2-row bands)
 PDT_API int pdt_stem_wgrad_v(const void* x4, const void* dA, const void* y, const float* bnc, float* slab, int N,
                              int H, int W, int Cout, int variant, hipStream_t stream) {

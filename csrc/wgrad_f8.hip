@@ -22,11 +22,6 @@
 #include "pdt_common.h"
 #include <stdlib.h>
 
-PDT_API int pdt_wgrad_reduce(float* slab, float* out, const float* bslab, float* bias_out, int splits, int Mo, int No,
-                             float scale, int accumulate, hipStream_t stream);
-PDT_API int pdt_wgrad_reduce_rows(const float* rows, float* out, int nrows, int n, float scale, int accumulate,
-                                  float* work, hipStream_t stream);
-
 namespace {
 
 typedef int i32x2 __attribute__((ext_vector_type(2)));

@@ -12,7 +12,9 @@ kernels read; gradients of parameters are produced in fp32.
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
+import re
 import threading
 import weakref
 from pathlib import Path
@@ -21,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import autotune
+from .build import CSRC
 
 _LIB_PATH = Path(os.environ.get("PDT_LIB_PATH", "") or
                  Path(__file__).resolve().parents[1] / "_lib" / "libpdt_hip.so")  # override: A/B builds
@@ -29,138 +32,54 @@ _lock = threading.Lock()
 
 c_int, c_long, c_float, c_double, c_void_p, c_uint = (ctypes.c_int, ctypes.c_long, ctypes.c_float,
                                                       ctypes.c_double, ctypes.c_void_p, ctypes.c_uint)
-P = c_void_p
 
-_SIGS = {
-    "pdt_conv_nt_ax": (c_int, [P] * 4 + [c_int] * 11 + [P] * 6 + [c_int] * 3 + [c_int] + [P] * 9 + [P]),
-    "pdt_conv_nt_ax2": (c_int, [P] * 4 + [c_int] * 25 + [P] * 6 + [c_int] * 3 + [c_int] + [P] * 9 + [P]),
-    "pdt_conv_nt_ax3": (c_int, [P] * 6 + [c_int] * 25 + [P] * 6 + [c_int] * 3 + [c_int] + [P] * 9 + [P]),
-    "pdt_stem_fwd_rows": (c_int, [c_int, c_int, c_int, c_int]),
-    "pdt_stem_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
-    "pdt_stem_wgrad_splits": (c_int, [c_int, c_int, c_int, c_int]),
-    "pdt_stem_wgrad": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
-    "pdt_stem_wgrad_v": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
-    "pdt_stem_wgrad_splits_v": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "pdt_conv_nt_stat_rows": (c_int, [c_int, c_int, c_int, c_int]),
-    "pdt_conv_nt_bnb_rows": (c_int, [c_int, c_int, c_int, c_int]),
-    "pdt_conv_nt_num_variants": (c_int, []),
-    "pdt_conv_nt_variant_kind": (c_int, [c_int]),
-    "pdt_conv_nt_resolve_variant": (c_int, [c_int, c_int, c_int, c_int]),
-    "pdt_conv_nt": (c_int, [P, P, P, P, P, P, P] + [c_int] * 25 + [P, c_int, c_int, P]),
-    "pdt_conv_nt_bnb": (c_int, [P] * 5 + [c_int] * 25 + [P] * 6 + [c_int] * 3 + [P]),
-    "pdt_conv_nt_bnb2": (c_int, [P] * 5 + [c_int] * 25 + [P] * 6 + [c_int] * 3 + [P] * 3 + [P]),
-    "pdt_conv_nt_bnb_supports": (c_int, [c_int] * 5),
-    "pdt_ln_fwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_float, P]),
-    "pdt_gemm_f8_q8": (c_int, [P] * 6 + [c_int] * 8 + [P, P, c_int, P, P, P, c_int, c_int, P, P]),
-    "pdt_gemm_f8_q8_cs": (c_int, [P] * 6 + [c_int] * 8 + [P, P, c_int, P, P, P, c_int, c_int, P, P, P]),
-    "pdt_gemm_f8_bm": (c_int, [c_int]),
-    "pdt_cast_cs_bands": (c_int, [c_int]),
-    "pdt_cast_fp8_delayed_cs": (c_int, [P, c_int, c_int, P, c_int, P, P, P, P, P]),
-    "pdt_wgrad_reduce_rows": (c_int, [P, P, c_int, c_int, c_float, c_int, P, P]),
-    "pdt_reduce_rows_work": (c_long, [c_int, c_int]),
-    "pdt_gemm_f8_q8_part": (c_long, [c_int, c_int]),
-    "pdt_ln_bwd_f8": (c_int, [P] * 9 + [c_int, c_int, c_int] + [P] * 6),
-    "pdt_ln_bwd_f8_db": (c_int, [P] * 9 + [c_int, c_int, c_int] + [P] * 7 + [c_int, P]),
-    "pdt_wgrad_f8_num_variants": (c_int, []),
-    "pdt_wgrad_f8_plan": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
-    "pdt_wgrad_f8_workspace": (c_long, [c_int, c_int, c_int]),
-    "pdt_linear_wgrad_f8": (c_int, [P] * 8 + [c_int] * 9 + [P]),
-    "pdt_bn_bwd_apply_dual": (c_int, [P] * 12 + [c_long, c_int, P]),
-    "pdt_bn_apply_res_affine": (c_int, [P] * 7 + [c_long, c_int, c_int, P, P]),
-    "pdt_ln_fwd_f8": (c_int, [P, P, P, P, P, P, c_int, c_int, c_float, P, P, P, P, P]),
-    "pdt_ln_add_fwd": (c_int, [P] * 8 + [c_int, c_int, c_float] + [P] * 5),
-    "pdt_ln_fwd_f8_blocks": (c_int, [c_int]),
-    "pdt_fp8_meta_roll_partial": (c_int, [P, P, c_int, c_int, P, P]),
-    "pdt_ln_bwd_blocks": (c_int, [c_int]),
-    "pdt_ln_bwd": (c_int, [P] * 9 + [c_int, c_int, c_int, P, P]),
-    "pdt_gelu_bwd": (c_int, [P, P, P, c_long, P]),
-    "pdt_wgrad_plan": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
-    "pdt_wgrad_plan2": (c_int, [c_int] * 7 + [ctypes.POINTER(c_int)]),
-    "pdt_wgrad_num_variants": (c_int, []),
-    "pdt_wgrad_halo_id": (c_int, []),
-    "pdt_wgrad_ring_id": (c_int, []),
-    "pdt_wgrad_workspace": (c_long, [c_int, c_int, c_int]),
-    "pdt_wgrad_reduce": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, c_int, P]),
-    "pdt_conv_wgrad": (c_int, [P, P, P, P] + [c_int] * 16 + [c_int, c_int, c_float, c_int, c_int, c_int, P, P]),
-    "pdt_conv_wgrad2": (c_int, [P, P, P, P] + [c_int] * 16 + [c_int, c_int, c_float, c_int, c_int, c_int, P, P, P,
-                                                                P]),
-    "pdt_bn_stats_blocks": (c_int, [c_long, c_int]),
-    "pdt_bn_bwd_reduce_pool": (c_int, [P] * 7 + [c_int] * 10 + [P]),
-    "pdt_bn_bwd_apply_pool": (c_int, [P] * 9 + [c_int] * 9 + [P]),
-    "pdt_rows_reduce_workspace": (c_long, [c_int, c_int]),
-    "pdt_bn_stats": (c_int, [P, P, c_long, c_int, c_int, P]),
-    "pdt_bn_finalize": (c_int, [P, c_int, c_int, c_double, c_float, c_float] + [P] * 9 + [P]),
-    "pdt_bn_apply": (c_int, [P, P, P, P, P, c_long, c_int, c_int, P, P]),
-    "pdt_bn_bwd_reduce": (c_int, [P, P, P, P, P, P, P, c_long, c_int, c_int, c_int, P, P]),
-    "pdt_bn_bwd_finalize": (c_int, [P, c_int, c_int, c_double] + [P] * 8 + [c_int, P]),
-    "pdt_bn_bwd_apply": (c_int, [P] * 10 + [c_long, c_int, c_int, P, P]),
-    "pdt_maxpool_fwd": (c_int, [P, P, P] + [c_int] * 9 + [P]),
-    "pdt_maxpool_fwd_affine": (c_int, [P] * 5 + [c_int] * 9 + [P]),
-    "pdt_maxpool_bwd": (c_int, [P, P, P] + [c_int] * 9 + [P]),
-    "pdt_maxpool_bwd_bnred": (c_int, [P] * 8 + [c_int] * 7 + [P]),
-    "pdt_avgpool_fwd": (c_int, [P, P, c_int, c_int, c_int, P]),
-    "pdt_avgpool_bwd": (c_int, [P, P, c_int, c_int, c_int, P]),
-    "pdt_xent_fwd": (c_int, [P, c_int, P, P, P, P, c_int, c_int, c_float, P]),
-    "pdt_xent_bwd": (c_int, [P, c_int, P, P, P, P, c_int, c_int, c_float, P]),
-    "pdt_colsum": (c_int, [P, P, P, c_int, c_int, c_int, P]),
-    "pdt_colsum_workspace": (c_long, [c_int, c_int]),
-    "pdt_chunk_struct_size": (c_int, []),
-    "pdt_sgd_step": (c_int, [P, c_int, P, P, P, P, c_float, c_float, c_float, c_float, c_int, c_int, c_float, P]),
-    "pdt_adam_step": (c_int, [P, c_int, P, P, P, P, P, P] + [c_float] * 5 + [c_int, c_float, c_float, c_float, P]),
-    "pdt_sgd_step2": (c_int, [P, c_int, P, P, P, P, c_float, c_float, c_float, c_float, c_int, c_int, c_float, P, P]),
-    "pdt_adam_step2": (c_int, [P, c_int, P, P, P, P, P, P] + [c_float] * 5 + [c_int, c_float, c_float, c_float, P,
-                                                                            c_int, P]),
-    "pdt_sumsq_chunks": (c_int, [P, c_int, P, P, P, P]),
-    "pdt_norm_finalize": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, c_float, P]),
-    "pdt_lars_step": (c_int, [P, c_int, P, P, P, P, P, P, c_int, P, c_float, c_float, c_float, c_int, c_float,
-                              c_float, P, P]),
-    "pdt_lamb_tick": (c_int, [P, c_double, c_double, P]),
-    "pdt_lamb_stage1": (c_int, [P, c_int, P, P, P, P, P, P, P] + [c_float] * 8 + [P, P]),
-    "pdt_lamb_stage2": (c_int, [P, c_int, P, P, P, P, P, P, c_int] + [c_float] * 5 + [P, P]),
-    "pdt_fill_uniform_bf16": (c_int, [P, c_long, c_uint, P]),
-    "pdt_cast_f32_bf16": (c_int, [P, P, c_long, P]),
-    "pdt_synth_images_bf16": (c_int, [P, P, c_long, c_int, c_int, c_int, c_uint, P, c_int, P]),
-    "pdt_crop_resize_norm_u8_bf16": (c_int, [P, c_int, c_int, P, P, P, c_long, c_int, c_int, P, P, P]),
-    "pdt_lane_reduce_probe": (c_int, [P, P, c_int, P]),
-    "pdt_wt_dgrad": (c_int, [P, P] + [c_int] * 9 + [P]),
-    "pdt_transpose_cast": (c_int, [P, P, c_int, c_int, P]),
-    "pdt_wt_job_size": (c_int, []),
-    "pdt_wt_dgrad_multi": (c_int, [P, c_int, c_long, P]),
-    "pdt_add_bf16": (c_int, [P, P, P, c_long, P]),
-    "pdt_attn_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_float, P]),
-    "pdt_cls_attn_fwd": (c_int, [P, P, P, c_int, c_int, c_int, P]),
-    "pdt_gemm_ring": (c_int, [P] * 6 + [c_int] * 8 + [P]),
-    "pdt_cls_attn_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),
-    "pdt_attn_fwd_f8": (c_int, [P, P, P, c_int, c_int, c_int, c_float, P]),
-    "pdt_attn_fwd_tiles": (c_int, [P, P, P, c_int, c_int, c_int, c_float, P]),
-    "pdt_attn_set_bwd_single": (c_int, [c_int]),
-    "pdt_gemm_f8_num_variants": (c_int, []),
-    "pdt_gelu_dual_cast_fp8": (c_int, [P, c_long, P, c_int, P, P, P, P, P]),
-    "pdt_cast_fp8_gelu_grad_cs": (c_int, [P, P, c_int, c_int, P, c_int, P, P, P, P, P]),
-    "pdt_gemm_f8": (c_int, [P, P, P, P, P, P] + [c_int] * 8 + [P, P, c_int, P]),
-    "pdt_bn_set_unroll": (c_int, [c_int]),
-    "pdt_amax_blocks": (c_int, [c_long]),
-    "pdt_amax_partial": (c_int, [P, c_int, c_long, P, P]),
-    "pdt_cast_fp8": (c_int, [P, c_int, c_long, P, c_int, P, P, P]),
-    "pdt_cast_fp8_t": (c_int, [P, c_int, c_int, P, P, P]),
-    "pdt_attn_bwd_q8": (c_int, [P] * 6 + [c_int, c_int, c_int, c_float] + [P] * 5),
-    "pdt_attn_fwd_f8_q8": (c_int, [P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P]),
-    "pdt_cast_fp8_dual": (c_int, [P, c_int, c_int, P, P, P, P, P]),
-    "pdt_fp8_meta_words": (c_int, []),
-    "pdt_cast_fp8_delayed": (c_int, [P, c_int, c_long, P, c_int, P, P, P]),
-    "pdt_fp8_meta_seed": (c_int, [P, c_long, c_int, P, P]),
-    "pdt_attn_bwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_float, P]),
-    "pdt_attn_bwd_f8": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, P]),
-    "pdt_attn_bwd_f8_grid": (c_int, [c_int, c_int]),
-    "pdt_attn_bwd_f8_q8": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P, P, P]),
-    "pdt_attn_set_pv8": (c_int, [c_int]),
-    "pdt_attn_bwd_f8_debug": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, P, P]),
-    "pdt_lenet_grad_row": (c_int, [c_int]),
-    "pdt_lenet_fwd": (c_int, [P] * 9 + [c_int, c_int, c_int, c_float, c_float, c_uint, P, P, P, P]),
-    "pdt_lenet_bwd": (c_int, [P] * 9 + [c_int, c_int, c_int, c_float, c_float, c_uint, P, P, P, P]),
-    "pdt_nll_fwd": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P]),
-    "pdt_nll_bwd": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
-}
+# The library's C ABI is declared once, in ``csrc/pdt_api.h`` (the compiler checks every
+# definition against it); the ctypes signatures are read from that same file.
+_API_HEADER = CSRC / "pdt_api.h"
+_SCALARS = {"int": c_int, "long": c_long, "unsigned": c_uint, "float": c_float, "double": c_double,
+            "hipStream_t": c_void_p}
+_POINTEES = ("void", "float", "int", "long", "int64_t")
+_DECL = re.compile(r"^PDT_API\s+([^;()]*?)(\w+)\s*\(([^;()]*)\)\s*;", re.M)
+
+
+def _ctype(text: str, decl: str):
+    """ctypes type of a C return type or parameter written ``[const] T [*] [name]``."""
+    tok = [t for t in text.replace("*", " * ").split() if t != "const"]
+    pointer = tok[1:2] == ["*"]
+    name = tok[2:] if pointer else tok[1:]  # nothing, or the parameter's name
+    if tok and len(name) <= 1 and not set(name) & {"*", *_SCALARS, *_POINTEES}:
+        if pointer and tok[0] in _POINTEES:
+            return c_void_p
+        if not pointer and tok[0] in _SCALARS:
+            return _SCALARS[tok[0]]
+    raise TypeError(f"{_API_HEADER.name}: the type in {text.strip()!r} (declaration of {decl}) is outside the "
+                    "ABI's closed set")
+
+
+def parse_api(text: str) -> dict:
+    """``{name: (restype, [argtypes])}`` of every ``PDT_API <ret> name(<params>);`` in ``text``."""
+    sigs = {}
+    for ret, name, params in _DECL.findall(text):
+        if name in sigs:
+            raise ValueError(f"{_API_HEADER.name}: {name} is declared twice")
+        sigs[name] = (_ctype(ret, name), [_ctype(p, name) for p in params.split(",")] if params.strip() else [])
+    return sigs
+
+
+@functools.lru_cache(maxsize=None)
+def signatures() -> dict:
+    """The signature table of this tree's ``csrc/pdt_api.h`` (read once per process)."""
+    return parse_api(_API_HEADER.read_text())
+
+
+def bind(lib, names=None):
+    """Set ``restype`` / ``argtypes`` of the library's entry points (all of them, or ``names``) on
+    a ``ctypes.CDLL`` from the header; an entry point the library lacks is an AttributeError."""
+    sigs = signatures()
+    for name in sigs if names is None else names:
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = sigs[name]
+    return lib
 
 
 def lib_path() -> Path:
@@ -173,7 +92,7 @@ class OpTimer:
     the per-op, per-shape breakdown of a training step (scripts/op_profile.py). Query
     entry points (plans, row counts, workspace sizes) pass through untimed."""
     _QUERY = ("_rows", "_variants", "_plan", "_plan2", "_workspace", "_size", "_blocks", "_kind", "_resolve_variant",
-              "_part", "_words", "_grad_row", "_set_unroll", "_set_bwd_single")
+              "_part", "_words", "_grad_row", "_set_bwd_single")
 
     def __init__(self, lib):
         self._lib = lib
@@ -184,7 +103,7 @@ class OpTimer:
         fn = getattr(self._lib, name)
         if not name.startswith("pdt_") or name.endswith(self._QUERY):
             return fn
-        ints = [i for i, t in enumerate(_SIGS.get(name, (None, []))[1]) if t in (c_int, c_long, c_uint)]
+        ints = [i for i, t in enumerate(signatures().get(name, (None, []))[1]) if t in (c_int, c_long, c_uint)]
 
         def call(*args):
             if not self.enabled or _capturing():
@@ -219,11 +138,7 @@ def _load():
             if not _LIB_PATH.exists():
                 raise RuntimeError(f"native kernel library missing: {_LIB_PATH} -- run "
                                    "`python -m pytorch_distributed_template_amd.ops.build`")
-            lib = ctypes.CDLL(str(_LIB_PATH))
-            for name, (res, args) in _SIGS.items():
-                fn = getattr(lib, name)
-                fn.restype = res
-                fn.argtypes = args
+            lib = bind(ctypes.CDLL(str(_LIB_PATH)))
             _lib = OpTimer(lib) if os.environ.get("PDT_OP_TIMING", "0") == "1" else lib
     return _lib
 

@@ -2,9 +2,13 @@
 bench shape (B=1024, T=197, H=12), forward and backward, with HIP events."""
 import ctypes
 import json
+import os
 import sys
 
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pytorch_distributed_template_amd.ops import native_ops  # noqa: E402
 
 B, T, H = 1024, 197, 12
 
@@ -23,10 +27,8 @@ def timed(fn, iters=50):
 
 
 def main():
-    lib = ctypes.CDLL(sys.argv[1])  # a .so holding pdt_cls_attn_fwd / _bwd (A/B: old vs new build)
-    P, I = ctypes.c_void_p, ctypes.c_int
-    lib.pdt_cls_attn_fwd.argtypes = [P, P, P, I, I, I, P]
-    lib.pdt_cls_attn_bwd.argtypes = [P, P, P, P, P, I, I, I, P]
+    # a .so holding pdt_cls_attn_fwd / _bwd (A/B: old vs new build), bound with this tree's header
+    lib = native_ops.bind(ctypes.CDLL(sys.argv[1]), ("pdt_cls_attn_fwd", "pdt_cls_attn_bwd"))
     s = torch.cuda.current_stream().cuda_stream
     torch.manual_seed(0)
     qkv = (torch.randn(B, T, 3 * H * 64, device="cuda") * 0.5).to(torch.bfloat16)

@@ -134,7 +134,7 @@ def gemm_floor(name, k):
             by += 2.0 * M * Ncol  # y (BN-backward partials) / the second A operand or the written copy
         if name.endswith("bnb2"):
             by += 2.0 * M * Ncol
-    elif name == "pdt_conv_wgrad" or name == "pdt_conv_wgrad_bn":
+    elif name == "pdt_conv_wgrad2":
         M, Mo, No = k[:3]
         Hs, Ws, C, Hm, Wm = k[4:9]
         fl = 2.0 * M * Mo * No

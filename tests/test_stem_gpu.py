@@ -66,7 +66,7 @@ def test_stem_halo_in_the_model_matches_generic(monkeypatch):
 @pytest.mark.parametrize("variant", [0, 1])
 @pytest.mark.parametrize("N", [2, 40])
 def test_stem_halo_weight_gradient_with_bn_backward_apply(N, variant):
-    """pdt_stem_wgrad (+ pdt_wgrad_reduce) = the stem weight gradient of dy = k1 * relu_gate(dA)
+    """pdt_stem_wgrad_v (+ pdt_wgrad_reduce) = the stem weight gradient of dy = k1 * relu_gate(dA)
     + k2 * y + k3 (gate from y * scale + shift > 0), dy rounded to bf16 as the kernel stages it."""
     lib = no._load()
     dev = "cuda"
