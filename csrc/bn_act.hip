@@ -496,6 +496,9 @@ int grid_for(long n8, int C) {
 
 PDT_API int pdt_bn_stats_blocks(long M, int C) {
   int cpr = C / 8;
+  // C < 8 (cpr == 0) or C / 8 > NT (rp == 0) would divide by zero here, on the host; answer 1
+  // and let pdt_bn_bwd_reduce, which takes this block count, refuse the shape with -1
+  if (cpr < 1 || cpr > NT) return 1;
   int rp = NT / cpr;
   long b = (M + rp - 1) / rp;
   // several blocks per CU, each streaming many rows (PDT_BN_BLOCKS overrides the cap)
@@ -608,7 +611,7 @@ PDT_API int pdt_bn_apply_res_affine(const void* y, const void* r, void* out, con
 PDT_API int pdt_bn_bwd_reduce(const void* dA, const void* y, const void* act, const float* mean,
                               const float* scale, const float* shift, float* part, long M, int C, int relu,
                               int blocks, const void* mask, hipStream_t st) {
-  if (C % 8 || C / 8 > NT) return -1;
+  if (C < 8 || C % 8 || C / 8 > NT) return -1;
   const u16 *G = (const u16*)dA, *Y = (const u16*)y, *A = (const u16*)act;
   const uint8_t* MK = (const uint8_t*)mask;
   dim3 g(blocks), b(NT);

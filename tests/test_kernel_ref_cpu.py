@@ -1,0 +1,421 @@
+"""tests/kernel_ref.py checked without a GPU:
+
+* every float64 reference against PyTorch's own float64 CPU op at 1e-12 relative;
+* every metric rejects a seeded fault and accepts a faithful fp32 emulation of the kernel
+  (torch fp32 on the CPU, output cast to bf16);
+* every exact-family input really is exact: its fp32 emulation equals the float64 reference.
+"""
+import pytest
+import torch
+import torch.nn.functional as F
+
+import kernel_ref as kr
+
+CPU = torch.device("cpu")
+BF = torch.bfloat16
+
+
+def rel(a, b):
+    return ((a - b).abs().max() / b.abs().max().clamp_min(1e-300)).item()
+
+
+def g(seed):
+    return kr.gen(seed, CPU)
+
+
+def trunc_bf16(x32):
+    """fp32 -> bf16 by dropping the low 16 bits (the seeded rounding fault)."""
+    return (x32.contiguous().view(torch.int32) & -65536).view(torch.float32).to(BF)
+
+
+# ------------------------------------------------------------ references against torch fp64
+@pytest.mark.parametrize("relu", [False, True])
+def test_bn_refs_match_torch(relu):
+    gg = g(0)
+    N, C, H = 5, 24, 6
+    x = (torch.randn(N, C, H, H, generator=gg, dtype=kr.F64) * 1.5 + 0.3).requires_grad_()
+    w = (torch.rand(C, generator=gg, dtype=kr.F64) + 0.5).requires_grad_()
+    b = torch.randn(C, generator=gg, dtype=kr.F64).requires_grad_()
+    rm, rv = torch.randn(C, generator=gg, dtype=kr.F64), torch.rand(C, generator=gg, dtype=kr.F64) + 0.5
+    rm0, rv0 = rm.clone(), rv.clone()
+    dA = torch.randn(N, C, H, H, generator=gg, dtype=kr.F64)
+    out = F.batch_norm(x, rm, rv, w, b, training=True, momentum=0.1, eps=1e-5)
+    if relu:
+        out = F.relu(out)
+    (out * dA).sum().backward()
+
+    def rows(t):  # NCHW -> [M][C]
+        return t.detach().permute(0, 2, 3, 1).reshape(-1, C)
+
+    M = N * H * H
+    x2 = rows(x)
+    fin = kr.bn_finalize_ref(kr.bn_partials(x2), M, 1e-5, 0.1, w, b, rm0, rv0, 7)
+    assert fin["nbt"] == 8
+    assert rel(fin["running_mean"], rm) < 1e-12 and rel(fin["running_var"], rv) < 1e-12
+    o, terms = kr.bn_apply_ref(x2, fin["scale"], fin["shift"], relu=relu)
+    assert rel(o, rows(out)) < 1e-12
+    assert bool((terms >= o.abs() - 1e-12).all())
+    gate = (o > 0) if relu else None
+    s, q, _, _ = kr.bn_bwd_sums_ref(rows(dA), x2, gate, fin["mean"])
+    bw = kr.bn_bwd_finalize_ref(s, q, M, w, fin["mean"], fin["invstd"])
+    assert rel(bw["dgamma"], w.grad) < 1e-12 and rel(bw["dbeta"], b.grad) < 1e-12
+    dy, _, dres = kr.bn_bwd_apply_ref(rows(dA), x2, gate, bw["k1"], bw["k2"], bw["k3"])
+    assert rel(dy, rows(x.grad)) < 1e-11  # (two cancellations deep: 1e-11 of max |dx|)
+    assert torch.equal(dres, rows(dA) * (gate.to(kr.F64) if relu else 1.0))
+
+
+def test_bn_apply_ref_residual_forms():
+    gg = g(1)
+    y, r = torch.randn(9, 8, generator=gg, dtype=kr.F64), torch.randn(9, 8, generator=gg, dtype=kr.F64)
+    sc, sh, rs, rb = (torch.randn(8, generator=gg, dtype=kr.F64) for _ in range(4))
+    o, t = kr.bn_apply_ref(y, sc, sh, r, relu=True)
+    assert rel(o, F.relu(y * sc + sh + r)) < 1e-12 and bool((t >= o).all())
+    o, t = kr.bn_apply_ref(y, sc, sh, r, rs, rb)
+    assert rel(o, y * sc + sh + (r * rs + rb)) < 1e-12
+
+
+def test_relu_mask_ref_bits_and_zeros():
+    out = torch.tensor([1.0, -1.0, 0.0, -0.0, 2.0, 0.0, -3.0, 5.0] + [0.0] * 7 + [1.0], dtype=kr.F64)
+    m = kr.relu_mask_ref(out)
+    assert m.tolist() == [1 | 16 | 128, 128]
+    assert torch.equal(kr.mask_to_gate(m, (16,)), out > 0)
+
+
+@pytest.mark.parametrize("k,s,p", [(2, 2, 0), (3, 1, 1), (3, 2, 0), (3, 2, 1), (2, 3, 0), (5, 3, 2)])
+@pytest.mark.parametrize("H,W", [(5, 7), (8, 9)])
+@pytest.mark.parametrize("ties", [False, True])
+def test_maxpool_refs_match_torch(k, s, p, H, W, ties):
+    gg = g(2)
+    N, C = 2, 8
+    x = torch.randn(N, H, W, C, generator=gg, dtype=kr.F64)
+    if ties:  # ReLU-like: ~60 % exact zeros
+        x = (x - 0.25).clamp_min(0.0)
+    xn = x.permute(0, 3, 1, 2).contiguous().requires_grad_()
+    y_t, flat = F.max_pool2d(xn, k, s, p, return_indices=True)
+    y, idx = kr.maxpool_fwd_ref(x, k, s, p)
+    Ho, Wo = y.shape[1:3]
+    assert (Ho, Wo) == tuple(y_t.shape[2:])
+    assert torch.equal(y, y_t.detach().permute(0, 2, 3, 1))
+    oh = torch.arange(Ho).view(1, 1, Ho, 1)
+    ow = torch.arange(Wo).view(1, 1, 1, Wo)
+    kh, kw = flat // W - (oh * s - p), flat % W - (ow * s - p)
+    assert torch.equal(idx.to(torch.int64), (kh * k + kw).permute(0, 2, 3, 1))
+    dy = torch.randn(N, Ho, Wo, C, generator=gg, dtype=kr.F64)
+    (y_t * dy.permute(0, 3, 1, 2)).sum().backward()
+    dx, ab = kr.maxpool_bwd_ref(dy, idx, H, W, k, s, p)
+    assert rel(dx, xn.grad.permute(0, 2, 3, 1)) < 1e-12
+    assert bool((ab >= dx.abs() - 1e-12).all())
+
+
+def test_maxpool_ref_1x1_and_uncovered_pixels():
+    x = torch.tensor([[[[3.0]]]], dtype=kr.F64)
+    y, idx = kr.maxpool_fwd_ref(x, 3, 2, 1)
+    assert y.item() == 3.0 and idx.item() == 4
+    # k < s: input rows / columns 2 (mod 3) lie in no window
+    x = torch.randn(1, 5, 7, 8, generator=g(3), dtype=kr.F64)
+    y, idx = kr.maxpool_fwd_ref(x, 2, 3, 0)
+    dx, _ = kr.maxpool_bwd_ref(torch.ones_like(y), idx, 5, 7, 2, 3, 0)
+    assert dx[:, 2].abs().sum() == 0 and dx[:, :, 2].abs().sum() == 0 and dx[:, :, 5].abs().sum() == 0
+    assert dx.sum() == y.numel()
+
+
+def test_avgpool_refs_match_torch():
+    x = torch.randn(3, 50, 24, generator=g(4), dtype=kr.F64)
+    xn = x.permute(0, 2, 1).reshape(3, 24, 5, 10).contiguous().requires_grad_()
+    y_t = F.adaptive_avg_pool2d(xn, 1)
+    y, _ = kr.avgpool_fwd_ref(x)
+    assert rel(y, y_t.detach().reshape(3, 24)) < 1e-12
+    dy = torch.randn(3, 24, generator=g(5), dtype=kr.F64)
+    (y_t.reshape(3, 24) * dy).sum().backward()
+    dx, _ = kr.avgpool_bwd_ref(dy, 50)
+    assert rel(dx, xn.grad.reshape(3, 24, 50).permute(0, 2, 1)) < 1e-12
+
+
+@pytest.mark.parametrize("D", [256, 768])
+def test_layernorm_refs_match_torch(D):
+    gg = g(6)
+    x = (torch.randn(7, D, generator=gg, dtype=kr.F64) * 2 + 1).requires_grad_()
+    w = torch.randn(D, generator=gg, dtype=kr.F64).requires_grad_()
+    b = torch.randn(D, generator=gg, dtype=kr.F64).requires_grad_()
+    dy, add = torch.randn(7, D, generator=gg, dtype=kr.F64), torch.randn(7, D, generator=gg, dtype=kr.F64)
+    y_t = F.layer_norm(x, (D,), w, b, 1e-6)
+    (y_t * dy).sum().backward()
+    fw = kr.ln_fwd_ref(x, w, b, 1e-6)
+    assert rel(fw["y"], y_t.detach()) < 1e-12
+    dg0, db0 = torch.randn(D, generator=gg, dtype=kr.F64), torch.randn(D, generator=gg, dtype=kr.F64)
+    bw = kr.ln_bwd_ref(dy, x, w, fw["mean"], fw["rstd"])
+    assert rel(bw["dx"], x.grad) < 1e-12 and rel(bw["dgamma"], w.grad) < 1e-12 and rel(bw["dbeta"], b.grad) < 1e-12
+    bw2 = kr.ln_bwd_ref(dy, x, w, fw["mean"], fw["rstd"], add, dg0, db0)
+    assert rel(bw2["dx"], x.grad + add) < 1e-12
+    assert rel(bw2["dgamma"], w.grad + dg0) < 1e-12 and rel(bw2["dbeta"], b.grad + db0) < 1e-12
+
+
+def test_gelu_grad_ref_matches_torch():
+    z = torch.cat([torch.tensor([0.0, 0.5, -0.5, 3.0, -3.0, 10.0, -10.0], dtype=kr.F64),
+                   torch.randn(1000, generator=g(7), dtype=kr.F64) * 2]).requires_grad_()
+    F.gelu(z, approximate="tanh").sum().backward()
+    assert rel(kr.gelu_tanh_grad_ref(z), z.grad) < 1e-12
+
+
+@pytest.mark.parametrize("V", [2, 63, 1001])
+@pytest.mark.parametrize("eps", [0.0, 0.1])
+def test_xent_ref_matches_torch(V, eps):
+    gg = g(8)
+    B = 5
+    x = (torch.randn(B, V, generator=gg, dtype=kr.F64) * 3).requires_grad_()
+    t = torch.randint(0, V, (B,), generator=gg)
+    t[0], t[1] = 0, V - 1
+    loss = F.cross_entropy(x, t, label_smoothing=eps)
+    (loss * 1.7).backward()
+    r = kr.xent_ref(x, t, eps, gout=1.7)
+    assert rel(r["lse"], torch.logsumexp(x.detach(), 1)) < 1e-12
+    assert rel(r["loss"], loss.detach()) < 1e-12
+    assert rel(r["loss_rows"], F.cross_entropy(x.detach(), t, label_smoothing=eps, reduction="none")) < 1e-12
+    assert rel(r["dlogits"], x.grad) < 1e-12
+
+
+def test_colsum_ref():
+    x = torch.randn(33, 10, generator=g(9), dtype=kr.F64)
+    o0 = torch.randn(10, generator=g(10), dtype=kr.F64)
+    s, a = kr.colsum_ref(x, o0)
+    assert rel(s, x.sum(0) + o0) < 1e-12 and bool((a >= s.abs()).all())
+
+
+# ------------------------------------------------------- fp32 emulations of the kernels (CPU)
+def emu_bn_apply(y, sc, sh, res=None, relu=False):
+    o = y.float() * sc + sh
+    if res is not None:
+        o = o + res.float()
+    return o.clamp_min(0.0) if relu else o
+
+
+def emu_bn_bwd_sums(dA, y, mean, drop=None):
+    gq, t = dA.float(), dA.float() * (y.float() - mean)
+    if drop is not None:
+        keep = torch.ones(dA.shape[0], dtype=torch.bool)
+        keep[drop] = False
+        gq, t = gq[keep], t[keep]
+    return gq.sum(0), t.sum(0)
+
+
+def emu_ln_bwd(d, addend=True):
+    dy, x, gm = d["dy"].float(), d["x"].float(), d["gamma"]
+    D = x.shape[1]
+    xh = (x - d["mean"][:, None]) * d["rstd"][:, None]
+    gy = dy * gm
+    m1, m2 = gy.sum(1, keepdim=True) * (1.0 / D), (gy * xh).sum(1, keepdim=True) * (1.0 / D)
+    dx = d["rstd"][:, None] * (gy - m1 - xh * m2)
+    if addend:
+        dx = dx + d["addend"].float()
+    return dx.to(BF), (dy * xh).sum(0), dy.sum(0)
+
+
+def emu_maxpool(x, k, s, p, last_wins=False):
+    """fp32 window scan in the kernel's order; ``last_wins``: the seeded tie-break fault."""
+    N, H, W, C = x.shape
+    Ho, Wo = kr.pool_out(H, k, s, p), kr.pool_out(W, k, s, p)
+    best = torch.full((N, Ho, Wo, C), float("-inf"))
+    idx = torch.zeros((N, Ho, Wo, C), dtype=torch.uint8)
+    for oh in range(Ho):
+        for ow in range(Wo):
+            for kh in range(k):
+                for kw in range(k):
+                    ih, iw = oh * s - p + kh, ow * s - p + kw
+                    if 0 <= ih < H and 0 <= iw < W:
+                        v = x[:, ih, iw].float()
+                        take = (v >= best[:, oh, ow]) if last_wins else (v > best[:, oh, ow])
+                        best[:, oh, ow] = torch.where(take, v, best[:, oh, ow])
+                        idx[:, oh, ow] = torch.where(take, torch.full_like(idx[:, oh, ow], kh * k + kw),
+                                                     idx[:, oh, ow])
+    return best.to(BF), idx
+
+
+# ---------------------------------------------------------- the exact family really is exact
+def test_exact_family_bn():
+    gg = g(20)
+    for R, C in [(1, 8), (257, 24), (2049, 72)]:
+        part = kr.exact_partials(R, C, gg)
+        # the fp32 sums are exact; the mean (a quotient by 16 R) is then one rounding of the fp64 value
+        kr.assert_exact(part[0].sum(0), kr.f64(part)[0].sum(0), "sum")
+        kr.assert_exact(part[1].sum(0), kr.f64(part)[1].sum(0), "sum of squares")
+        fin = kr.bn_finalize_ref(kr.f64(part), 16.0 * R, 1e-5)
+        assert torch.equal((part[0].sum(0).double() / (16.0 * R)).float(), fin["mean"].float())
+    dA, y, mean = kr.exact_bn_bwd_inputs(40001, 24, gg)
+    s, q, _, _ = kr.bn_bwd_sums_ref(dA, y, None, mean)
+    es, eq = emu_bn_bwd_sums(dA, y, mean)
+    kr.assert_exact(es, s, "sum g")
+    kr.assert_exact(eq, q, "sum g (y - mean)")
+    gate = y > 0
+    s, q, _, _ = kr.bn_bwd_sums_ref(dA, y, gate, mean)
+    es, eq = emu_bn_bwd_sums(dA * gate, y, mean)
+    kr.assert_exact(es, s, "gated sum g")
+    kr.assert_exact(eq, q, "gated sum g (y - mean)")
+
+
+def test_exact_family_pool_and_colsum():
+    gg = g(21)
+    x = kr.ints((5, 16, 72), gg)
+    y, _ = kr.avgpool_fwd_ref(x)
+    kr.assert_exact((x.float().sum(1) * (1.0 / 16)).to(BF), y, "avgpool fwd")
+    dy = kr.ints((5, 72), gg)
+    dx, _ = kr.avgpool_bwd_ref(dy, 16)
+    kr.assert_exact((dy.float() * (1.0 / 16))[:, None, :].expand(-1, 16, -1).to(BF), dx, "avgpool bwd")
+    x = kr.ints((16417, 10), gg)
+    s, _ = kr.colsum_ref(x, kr.f64(kr.ints((10,), gg, dtype=torch.float32)))
+    # (the same generator state cannot be replayed: accumulate into zeros instead)
+    s0, _ = kr.colsum_ref(x)
+    kr.assert_exact(x.float().sum(0), s0, "colsum")
+    xs = kr.ints((2, 8, 9, 8), gg)
+    yv, idx = kr.maxpool_fwd_ref(xs, 3, 1, 1)
+    dyi = kr.ints(tuple(yv.shape), gg)
+    dxr, _ = kr.maxpool_bwd_ref(dyi, idx, 8, 9, 3, 1, 1)
+    kr.assert_exact(dxr.to(torch.float32).to(BF), dxr, "maxpool bwd: up to 9 integers <= 8 fit bf16")
+    del s
+
+
+@pytest.mark.parametrize("D", [256, 512, 768, 1024])
+def test_exact_family_layernorm_bwd(D):
+    d = kr.exact_ln_bwd_inputs(197, D, g(22))
+    ref = kr.ln_bwd_ref(d["dy"], d["x"], d["gamma"], d["mean"], d["rstd"], d["addend"])
+    dx, dg, db = emu_ln_bwd(d)
+    kr.assert_exact(dg, ref["dgamma"], "dgamma")
+    kr.assert_exact(db, ref["dbeta"], "dbeta")
+    if D != 768:  # 1/768 is not a power of two: the row means round
+        kr.assert_exact(dx, ref["dx"], "dx")
+    else:
+        kr.assert_bf16_close(dx, ref["dx"], ref["dx_abs"], "dx", extra=2 * 20 * kr.U * ref["dx_mean_abs"])
+
+
+# ------------------------------------------------- metrics: accept the faithful, reject faults
+def _apply_case(M=4160, C=256):
+    gg = g(30)
+    y, r = kr.normal((M, C), gg), kr.normal((M, C), gg)
+    sc, sh = torch.rand(C, generator=gg) + 0.5, torch.randn(C, generator=gg) * 0.5
+    ref, terms = kr.bn_apply_ref(y, sc, sh, r)
+    return emu_bn_apply(y, sc, sh, r), ref, terms
+
+
+def test_rounding_metrics_accept_rne_reject_truncation():
+    o32, ref, terms = _apply_case()
+    assert ref.numel() >= 2 ** 20
+    kr.assert_bf16_close(o32.to(BF), ref, terms, "rne")
+    kr.assert_unbiased_rounding(o32.to(BF), ref, "rne")
+    bias, _ = kr.rounding_bias(o32.to(BF), ref)
+    assert abs(bias) < 0.002
+    with pytest.raises(AssertionError):
+        kr.assert_unbiased_rounding(trunc_bf16(o32), ref, "trunc")
+    bias, _ = kr.rounding_bias(trunc_bf16(o32), ref)
+    assert -0.52 < bias < -0.48
+    with pytest.raises(AssertionError):
+        kr.assert_bf16_close(trunc_bf16(o32), ref, terms, "trunc")
+    with pytest.raises(AssertionError):  # too few elements to judge a bias
+        kr.assert_unbiased_rounding(o32.to(BF)[:100], ref[:100], "short")
+
+
+def test_exact_metric_rejects_one_dropped_row_of_40000():
+    dA, y, mean = kr.exact_bn_bwd_inputs(40000, 8, g(31))
+    dA[12345] = 1  # (a row that certainly contributes)
+    s, q, _, _ = kr.bn_bwd_sums_ref(dA, y, None, mean)
+    es, eq = emu_bn_bwd_sums(dA, y, mean)
+    kr.assert_exact(es, s)
+    kr.assert_exact(eq, q)
+    es, eq = emu_bn_bwd_sums(dA, y, mean, drop=12345)
+    with pytest.raises(AssertionError):
+        kr.assert_exact(es, s)
+    # ... which a Frobenius-norm tolerance cannot see
+    assert ((es.double() - s).norm() / s.norm()).item() < 2e-2
+
+
+def test_unwritten_last_row_is_rejected():
+    o32, ref, terms = _apply_case(64, 8)
+    out = kr.guarded(o32.shape, BF, CPU)
+    out.copy_(o32.to(BF))
+    kr.assert_bf16_close(out, ref, terms, "all rows")
+    kr.check_guards()
+    out = kr.guarded(o32.shape, BF, CPU)
+    out[:-1].copy_(o32.to(BF)[:-1])
+    with pytest.raises(AssertionError):
+        kr.assert_bf16_close(out, ref, terms, "last row unwritten")
+    with pytest.raises(AssertionError):
+        kr.assert_exact(out, kr.f64(o32.to(BF)), "last row unwritten")
+    kr.check_guards()
+
+
+def test_mask_metric_rejects_one_flipped_bit():
+    o32, _, _ = _apply_case(64, 8)
+    out = o32.to(BF).clamp_min(0)
+    want = kr.relu_mask_ref(out)
+    kr.assert_exact(want.clone(), want, "mask")
+    bad = want.clone()
+    bad[17] ^= 4
+    with pytest.raises(AssertionError):
+        kr.assert_exact(bad, want, "mask")
+
+
+def test_argmax_metric_rejects_last_maximum():
+    for x in (torch.full((1, 5, 7, 8), 2.0).to(BF), (kr.normal((1, 5, 7, 8), g(32)).float() - 0.25).clamp_min(0).to(BF)):
+        y, idx = kr.maxpool_fwd_ref(x, 3, 2, 1)
+        ey, eidx = emu_maxpool(x, 3, 2, 1)
+        kr.assert_exact(ey, y, "values")
+        kr.assert_exact(eidx, idx, "argmax")
+        ey, eidx = emu_maxpool(x, 3, 2, 1, last_wins=True)
+        kr.assert_exact(ey, y, "values are the same whichever maximum is taken")
+        with pytest.raises(AssertionError):
+            kr.assert_exact(eidx, idx, "argmax")
+
+
+def test_guard_band_catches_store_past_the_end():
+    for dtype, shape in [(BF, (37, 24)), (torch.float32, (2, 3, 10)), (torch.uint8, (5,))]:
+        t = kr.guarded(shape, dtype, CPU)
+        assert t.data_ptr() % 16 == 0 and t.is_contiguous() and tuple(t.shape) == shape
+        t.fill_(1)
+        kr.check_guards()
+        t = kr.guarded(shape, dtype, CPU)
+        raw, nbytes = kr._live[-1]
+        assert raw.numel() - nbytes >= 512 and t.data_ptr() - raw.data_ptr() >= 256
+        raw[kr._FRONT + nbytes + 16] = 0  # one store 16 bytes past the end
+        with pytest.raises(AssertionError):
+            kr.check_guards()
+        t = kr.guarded(shape, dtype, CPU)
+        kr._live[-1][0][kr._FRONT - 1] = 0  # one byte before the start
+        with pytest.raises(AssertionError):
+            kr.check_guards()
+        assert kr._live == []
+
+
+def test_loss_mean_metric_rejects_b_plus_one():
+    gg = g(33)
+    B, V = 257, 1000
+    x = kr.normal((B, V), gg, torch.float32, std=3.0)
+    t = torch.randint(0, V, (B,), generator=gg)
+    r = kr.xent_ref(x, t, 0.1)
+    rows32 = F.cross_entropy(x, t, label_smoothing=0.1, reduction="none")
+    row_err = (rows32.double() - r["loss_rows"]).abs().max().item()
+    good = (rows32.sum() * (1.0 / B)).reshape(())
+    bad = (rows32.sum() * (1.0 / (B + 1))).reshape(())
+    kr.assert_f32_close(good, r["loss"], r["loss_rows"].abs().mean(), "mean", roundings=12, extra=row_err)
+    with pytest.raises(AssertionError):
+        kr.assert_f32_close(bad, r["loss"], r["loss_rows"].abs().mean(), "mean", roundings=12, extra=row_err)
+
+
+def test_bf16_close_accepts_emulations_of_each_family():
+    gg = g(34)
+    # LayerNorm forward, with a row of mean 100 / std 1 and a constant row
+    D = 768
+    x = kr.normal((6, D), gg)
+    x[1] = kr.normal((D,), gg, mean=100.0)
+    x[2] = 3.0
+    w, b = torch.randn(D, generator=gg), torch.randn(D, generator=gg)
+    fw = kr.ln_fwd_ref(x, w, b, 1e-6)
+    xf = x.float()
+    mean = xf.mean(1, keepdim=True)
+    rstd = torch.rsqrt(((xf - mean) ** 2).mean(1, keepdim=True) + 1e-6)
+    y = ((xf - mean) * rstd * w + b).to(BF)
+    kr.assert_bf16_close(y, fw["y"], fw["y_abs"], "ln fwd", roundings=20)
+    assert abs(fw["rstd"][2].item() - 1e3) < 1e-6 and torch.equal(y[2].float(), b.to(BF).float())
+    # max-pool backward, random gradients
+    xs = kr.normal((2, 8, 9, 8), gg)
+    yv, idx = kr.maxpool_fwd_ref(xs, 3, 1, 1)
+    dy = kr.normal(tuple(yv.shape), gg)
+    dx, ab = kr.maxpool_bwd_ref(dy, idx, 8, 9, 3, 1, 1)
+    kr.assert_bf16_close(dx.to(torch.float32).to(BF), dx, ab, "pool bwd")

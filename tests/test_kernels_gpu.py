@@ -1,6 +1,11 @@
 """Numerics of every HIP kernel against a plain PyTorch fp32 reference of the
 same op (inputs rounded to bf16 first, so only accumulation / output rounding
-differ). Run on an MI355X: ``pytest -m gpu tests/test_kernels_gpu.py``."""
+differ). Run on an MI355X: ``pytest -m gpu tests/test_kernels_gpu.py``.
+
+The element and row kernels (BatchNorm passes, pooling, LayerNorm, GELU backward, cross-entropy,
+column sums) are checked here only at a few shapes and with max-abs / Frobenius tolerances; their
+per-path tests against float64 references, with exact-family inputs, guard bands and derived
+bounds, are test_bn_act_kernels_gpu.py, test_pool_kernels_gpu.py and test_row_kernels_gpu.py."""
 import pytest
 import torch
 import torch.nn as nn
