@@ -51,6 +51,44 @@ struct PixelOut {
   uint32_t lo, hi;  // bf16 (c0, c1), (c2, 0)
 };
 
+struct Rgb {
+  float v[3];  // the bilinear sample, fp32 on the 0..255 scale
+};
+
+struct Taps {
+  uint32_t p00, p01, p10, p11;  // load_rgb of the four taps
+  float ly, lx;
+};
+
+__device__ __forceinline__ Taps load_taps(const uint8_t* __restrict__ img, uint32_t row0, uint32_t row1, int ix,
+                                          int ix1, float ly, float lx) {
+  return Taps{load_rgb(img, (row0 + (uint32_t)ix) * 3u), load_rgb(img, (row0 + (uint32_t)ix1) * 3u),
+              load_rgb(img, (row1 + (uint32_t)ix) * 3u), load_rgb(img, (row1 + (uint32_t)ix1) * 3u), ly, lx};
+}
+
+// sample()'s blend, operation for operation, without the normalization
+__device__ __forceinline__ Rgb blend_taps(const Taps& t) {
+  const float ly = t.ly, lx = t.lx;
+  const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
+  Rgb r;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float a = (float)((t.p00 >> (8 * c)) & 0xffu), b = (float)((t.p01 >> (8 * c)) & 0xffu);
+    const float d = (float)((t.p10 >> (8 * c)) & 0xffu), e = (float)((t.p11 >> (8 * c)) & 0xffu);
+    r.v[c] = fmaf(w11, e, fmaf(w10, d, fmaf(w01, b, w00 * a)));
+  }
+  return r;
+}
+
+// normalize and round once, to bf16
+__device__ __forceinline__ PixelOut finish(const Rgb& r, float m0, float m1, float m2, float s0, float s1, float s2) {
+  constexpr float K = 1.f / 255.f;
+  PixelOut o;
+  o.lo = pack2bf((fmaf(r.v[0], K, -m0)) * s0, (fmaf(r.v[1], K, -m1)) * s1);
+  o.hi = pack2bf((fmaf(r.v[2], K, -m2)) * s2, 0.f);
+  return o;
+}
+
 __device__ __forceinline__ PixelOut sample(const uint8_t* __restrict__ img, uint32_t row0, uint32_t row1, int ix,
                                            int ix1, float ly, float lx, float m0, float m1, float m2, float s0,
                                            float s1, float s2) {
@@ -73,12 +111,63 @@ __device__ __forceinline__ PixelOut sample(const uint8_t* __restrict__ img, uint
   return o;
 }
 
+// One augmented view: an image and its crop box. Wave-uniform as loaded; a CutMix lane holds its
+// own choice of two.
+struct View {
+  const uint8_t* img;
+  int y0, x0, h, w, flip;
+};
+
+// The loaded taps of output pixel (oy, ox) of view v, formed from scratch (CutMix: the lane's
+// two pixels may read different views).
+__device__ __forceinline__ Taps view_taps(const View& v, int oy, int ox, int Ws, int S, int S2, float inv2S) {
+  int iy, iy1, ix, ix1;
+  float ly, lx;
+  axis_taps(oy, v.h, S, S2, inv2S, iy, iy1, ly);
+  axis_taps(v.flip ? S - 1 - ox : ox, v.w, S, S2, inv2S, ix, ix1, lx);
+  const uint32_t row0 = (uint32_t)((v.y0 + iy) * Ws + v.x0), row1 = (uint32_t)((v.y0 + iy1) * Ws + v.x0);
+  return load_taps(v.img, row0, row1, ix, ix1, ly, lx);
+}
+
+// Mixup / CutMix operands of output b (MIX kernels): the partner's augmented view -- its gather
+// index and its own box and flip --, the cut rectangle (y0, x0, y1, x1), half-open, in output
+// coordinates, and the weight of the own pixels outside it.
+struct MixArgs {
+  const int64_t* pidx;
+  const int* pbox;
+  const int* rect;
+  const float* w_own;
+};
+struct NoMix {};
+
+// The kernel's store, for the mixing paths: 4 bf16 (8 bytes) per padded pixel, 64-bit pixel index
+__device__ __forceinline__ void store_pair(u16* __restrict__ out, long pix, bool pair, PixelOut a, PixelOut c) {
+  uint2* o = reinterpret_cast<uint2*>(out) + pix;
+  if (pair) {
+    // 8-byte aligned always, 16-byte aligned for even S
+    typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
+    *reinterpret_cast<u32x4_a8*>(o) = u32x4_a8{a.lo, a.hi, c.lo, c.hi};
+  } else {
+    *o = uint2{a.lo, a.hi};
+  }
+}
+
 // grid.x = B * nblk: workgroup (b, k) covers pixel pairs [k NT, (k+1) NT) of image b's S * P
 // pairs (P = ceil(S / 2) pairs per output row).
+//
+// MIX: per output pixel, inside the rectangle the partner's sample; else, at w_own == 1, the own
+// sample; else fma(w_own, own, (1 - w_own) partner) on the fp32 0..255 values (one rounding, to
+// bf16, as without mixing). w_own, the rectangle and the partner's box and base are
+// wave-uniform, so the three cases are scalar branches; the rectangle test is per lane and per
+// pixel (a lane's two pixels can lie on either side of an edge):
+//   * nothing to mix (w_own == 1, empty rectangle): the plain path, instruction for instruction;
+//   * CutMix (w_own == 1): each pixel selects its view -- image base and box -- and samples once;
+//   * Mixup: both pixels' taps of both views are in flight together, then the blend.
+template <bool MIX, class Mix>
 __global__ void __launch_bounds__(NT)
 crop_resize_norm_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ idx, const int* __restrict__ box,
                         u16* __restrict__ out, long img_bytes, int Ws, int S, int P, uint32_t nblk, FastDiv dP,
-                        float inv2S, float m0, float m1, float m2, float s0, float s1, float s2) {
+                        float inv2S, float m0, float m1, float m2, float s0, float s1, float s2, Mix mix) {
   const uint32_t b = blockIdx.x / nblk;
   const uint32_t p = (blockIdx.x - b * nblk) * NT + threadIdx.x;
   if (p >= (uint32_t)(S * P)) return;
@@ -92,6 +181,49 @@ crop_resize_norm_kernel(const uint8_t* __restrict__ src, const int64_t* __restri
   const bool pair = ox0 + 1 < S;
   const int ox1 = pair ? ox0 + 1 : ox0;  // odd-S tail: the second pixel is computed and dropped
   const int S2 = 2 * S;
+
+  if constexpr (MIX) {
+    const int* rc = mix.rect + (long)b * 4;
+    const int ry0 = rc[0], rx0 = rc[1], ry1 = rc[2], rx1 = rc[3];
+    const float wo = mix.w_own[b];
+    if (wo != 1.f || (ry0 < ry1 && rx0 < rx1)) {
+      const int* pb = mix.pbox + (long)b * 5;
+      const View own{img, y0, x0, h, w, flip};
+      const View par{src + (long)mix.pidx[b] * img_bytes, pb[0], pb[1], pb[2], pb[3], pb[4]};
+      const long pix = ((long)b * S + oy) * S + ox0;
+      const bool iny = oy >= ry0 && oy < ry1;
+      const bool ina = iny && ox0 >= rx0 && ox0 < rx1, inc = iny && ox1 >= rx0 && ox1 < rx1;
+      if (wo == 1.f) {
+        const View va{ina ? par.img : own.img, ina ? par.y0 : own.y0, ina ? par.x0 : own.x0,
+                      ina ? par.h : own.h,     ina ? par.w : own.w,   ina ? par.flip : own.flip};
+        const View vc{inc ? par.img : own.img, inc ? par.y0 : own.y0, inc ? par.x0 : own.x0,
+                      inc ? par.h : own.h,     inc ? par.w : own.w,   inc ? par.flip : own.flip};
+        Taps ta = view_taps(va, oy, ox0, Ws, S, S2, inv2S), tc = view_taps(vc, oy, ox1, Ws, S, S2, inv2S);
+        // every load issued before the first use (the pin below, for the same reason)
+        asm volatile("" : "+v"(ta.p00), "+v"(ta.p01), "+v"(ta.p10), "+v"(ta.p11), "+v"(tc.p00), "+v"(tc.p01),
+                          "+v"(tc.p10), "+v"(tc.p11));
+        store_pair(out, pix, pair, finish(blend_taps(ta), m0, m1, m2, s0, s1, s2),
+                   finish(blend_taps(tc), m0, m1, m2, s0, s1, s2));
+        return;
+      }
+      // Mixup: both pixels' taps of both views, 16 loads in flight
+      Taps oa = view_taps(own, oy, ox0, Ws, S, S2, inv2S), oc = view_taps(own, oy, ox1, Ws, S, S2, inv2S);
+      Taps qa = view_taps(par, oy, ox0, Ws, S, S2, inv2S), qc = view_taps(par, oy, ox1, Ws, S, S2, inv2S);
+      asm volatile("" : "+v"(oa.p00), "+v"(oa.p01), "+v"(oa.p10), "+v"(oa.p11), "+v"(oc.p00), "+v"(oc.p01),
+                        "+v"(oc.p10), "+v"(oc.p11), "+v"(qa.p00), "+v"(qa.p01), "+v"(qa.p10), "+v"(qa.p11),
+                        "+v"(qc.p00), "+v"(qc.p01), "+v"(qc.p10), "+v"(qc.p11));
+      const Rgb ova = blend_taps(oa), ovc = blend_taps(oc), pva = blend_taps(qa), pvc = blend_taps(qc);
+      const float wp = 1.f - wo;
+      Rgb ra, rc2;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        ra.v[c] = ina ? pva.v[c] : fmaf(wo, ova.v[c], wp * pva.v[c]);
+        rc2.v[c] = inc ? pvc.v[c] : fmaf(wo, ovc.v[c], wp * pvc.v[c]);
+      }
+      store_pair(out, pix, pair, finish(ra, m0, m1, m2, s0, s1, s2), finish(rc2, m0, m1, m2, s0, s1, s2));
+      return;
+    }
+  }
 
   int iy, iy1;
   float ly;
@@ -118,6 +250,24 @@ crop_resize_norm_kernel(const uint8_t* __restrict__ src, const int64_t* __restri
     *o = uint2{a.lo, a.hi};
   }
 }
+
+template <bool MIX, class Mix>
+int launch(const void* src, int Hs, int Ws, const int64_t* idx, const int* box, Mix mix, void* out, long B, int S,
+           int Cp, const float* mean, const float* inv_std, hipStream_t st) {
+  if (!src || !box || !out || !mean || !inv_std) return -1;
+  if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || Cp != 4) return -1;
+  if (Hs > 32768 || Ws > 32768 || S > 16384) return -1;  // (2S+1) h fits an int
+  const long img_bytes = (long)Hs * Ws * 3;
+  if (img_bytes < 4 || img_bytes >= (1L << 31)) return -1;  // dword taps; 32-bit offsets in an image
+  const int P = (S + 1) / 2;
+  const long nblk = ((long)S * P + NT - 1) / NT;
+  if (B * nblk > 0x7fffffffL) return -1;
+  hipLaunchKernelGGL((crop_resize_norm_kernel<MIX, Mix>), dim3((unsigned)(B * nblk)), dim3(NT), 0, st,
+                     (const uint8_t*)src, idx, box, (u16*)out, img_bytes, Ws, S, P, (uint32_t)nblk,
+                     make_fastdiv((uint32_t)P), 1.f / (float)(2 * S), mean[0], mean[1], mean[2], inv_std[0],
+                     inv_std[1], inv_std[2], mix);
+  PDT_RETURN_LAUNCH();
+}
 }  // namespace
 
 // src: uint8 [n][Hs][Ws][3] (device); idx: int64 [B] source image of each output (device; null:
@@ -127,16 +277,16 @@ crop_resize_norm_kernel(const uint8_t* __restrict__ src, const int64_t* __restri
 PDT_API int pdt_crop_resize_norm_u8_bf16(const void* src, int Hs, int Ws, const int64_t* idx, const int* box, void* out,
                                          long B, int S, int Cp, const float* mean, const float* inv_std,
                                          hipStream_t st) {
-  if (!src || !box || !out || !mean || !inv_std) return -1;
-  if (B <= 0 || Hs <= 0 || Ws <= 0 || S <= 0 || Cp != 4) return -1;
-  if (Hs > 32768 || Ws > 32768 || S > 16384) return -1;  // (2S+1) h fits an int
-  const long img_bytes = (long)Hs * Ws * 3;
-  if (img_bytes < 4 || img_bytes >= (1L << 31)) return -1;  // dword taps; 32-bit offsets in an image
-  const int P = (S + 1) / 2;
-  const long nblk = ((long)S * P + NT - 1) / NT;
-  if (B * nblk > 0x7fffffffL) return -1;
-  hipLaunchKernelGGL(crop_resize_norm_kernel, dim3((unsigned)(B * nblk)), dim3(NT), 0, st, (const uint8_t*)src, idx,
-                     box, (u16*)out, img_bytes, Ws, S, P, (uint32_t)nblk, make_fastdiv((uint32_t)P),
-                     1.f / (float)(2 * S), mean[0], mean[1], mean[2], inv_std[0], inv_std[1], inv_std[2]);
-  PDT_RETURN_LAUNCH();
+  return launch<false>(src, Hs, Ws, idx, box, NoMix{}, out, B, S, Cp, mean, inv_std, st);
+}
+
+// The same with Mixup / CutMix (see the kernel): pidx int64 [B] the partner's source image, pbox
+// int32 [B][5] the partner's own box and flip, rect int32 [B][4] = y0, x0, y1, x1 (half-open,
+// inside [0, S]^2), w_own fp32 [B] in [0, 1]; all on the device and trusted like the boxes.
+PDT_API int pdt_crop_resize_norm_mix_u8_bf16(const void* src, int Hs, int Ws, const int64_t* idx, const int* box,
+                                             const int64_t* pidx, const int* pbox, const int* rect,
+                                             const float* w_own, void* out, long B, int S, int Cp, const float* mean,
+                                             const float* inv_std, hipStream_t st) {
+  if (!pidx || !pbox || !rect || !w_own) return -1;
+  return launch<true>(src, Hs, Ws, idx, box, MixArgs{pidx, pbox, rect, w_own}, out, B, S, Cp, mean, inv_std, st);
 }

@@ -189,6 +189,10 @@ PDT_API int pdt_gemm_ring_epi_pers(const void* a, const void* b, void* c, const 
 PDT_API int pdt_crop_resize_norm_u8_bf16(const void* src, int Hs, int Ws, const int64_t* idx, const int* box,
                                          void* out, long B, int S, int Cp, const float* mean, const float* inv_std,
                                          hipStream_t st);
+PDT_API int pdt_crop_resize_norm_mix_u8_bf16(const void* src, int Hs, int Ws, const int64_t* idx, const int* box,
+                                             const int64_t* pidx, const int* pbox, const int* rect,
+                                             const float* w_own, void* out, long B, int S, int Cp, const float* mean,
+                                             const float* inv_std, hipStream_t st);
 
 // layernorm.hip
 PDT_API int pdt_ln_fwd(const void* x, const float* g, const float* b, void* y, float* mean, float* rstd, int rows,
@@ -309,5 +313,11 @@ PDT_API int pdt_xent_fwd(const void* logits, int bf16, const long* target, float
                          float* loss_out, int B, int V, float eps, hipStream_t st);
 PDT_API int pdt_xent_bwd(const void* logits, int bf16, const long* target, const float* lse, const float* gout,
                          void* dlogits, int B, int V, float eps, hipStream_t st);
+PDT_API int pdt_xent_pair_fwd(const void* logits, int bf16, const long* ta, const long* tb, const float* lam,
+                              float* lse, float* loss_rows, float* loss_out, int B, int V, float eps,
+                              hipStream_t st);
+PDT_API int pdt_xent_pair_bwd(const void* logits, int bf16, const long* ta, const long* tb, const float* lam,
+                              const float* lse, const float* gout, void* dlogits, int B, int V, float eps,
+                              hipStream_t st);
 PDT_API long pdt_colsum_workspace(int R, int C);
 PDT_API int pdt_colsum(const void* x, float* out, float* work, int R, int C, int acc, hipStream_t st);

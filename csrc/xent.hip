@@ -7,6 +7,13 @@
 //           lse[row], loss[row] = lse - (1-eps)*x[t] - eps*mean(x)
 //           then a one-block deterministic mean over rows.
 // backward: dlogits = g/B * (softmax - (1-eps)*onehot - eps/V), bf16 out.
+//
+// Paired targets (Mixup / CutMix: pdt_xent_pair_*): a row has two labels ta, tb and a weight lam,
+//   loss[row]  = lse - (1-eps) * (lam*x[ta] + (1-lam)*x[tb]) - eps*mean(x)
+//   dlogits[j] = g/B * (p_j - eps/V - (1-eps) * (lam*[j==ta] + (1-lam)*[j==tb]))
+// the same kernels instantiated on the target kind (Hard / Pair) -- a dense [B][V] soft-target
+// matrix is never read. ta == tb counts as weight 1 on that label, so the coefficient is
+// exactly (1-eps); a row with ta or tb outside [0, V) contributes 0 and gets a zero gradient.
 #include "pdt_common.h"
 
 namespace {
@@ -19,9 +26,27 @@ __device__ __forceinline__ float ldv(const void* p, long i) {
   return reinterpret_cast<const float*>(p)[i];
 }
 
-template <bool BF16>
+// What a paired target adds to a row's label: the second label and the first one's weight
+// (the kernels' last argument; Hard: nothing, one hard label per row).
+struct Hard {
+  static constexpr bool pair = false;
+};
+struct Pair {
+  static constexpr bool pair = true;
+  const long* tb;
+  const float* lam;
+};
+
+// the weights (wa, wb) of a paired row's two labels
+__device__ __forceinline__ void pair_weights(long ta, long tb, float lam, float& wa, float& wb) {
+  wa = ta == tb ? 1.f : lam;
+  wb = ta == tb ? 0.f : 1.f - lam;
+}
+
+template <bool BF16, class Target>
 __global__ void xent_fwd_kernel(const void* __restrict__ logits, const long* __restrict__ target,
-                                float* __restrict__ lse, float* __restrict__ loss, int B, int V, float eps) {
+                                float* __restrict__ lse, float* __restrict__ loss, int B, int V, float eps,
+                                const Target second) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
   if (row >= B) return;
@@ -49,9 +74,18 @@ __global__ void xent_fwd_kernel(const void* __restrict__ logits, const long* __r
   if (lane == 0) {
     float l = m + __logf(s);
     lse[row] = l;
-    long t = target[row];
-    float xt = (t >= 0 && t < V) ? ldv<BF16>(logits, base + t) : 0.f;
-    loss[row] = (t >= 0 && t < V) ? (l - (1.f - eps) * xt - eps * (sx / V)) : 0.f;
+    if constexpr (Target::pair) {
+      const long ta = target[row], tb = second.tb[row];
+      const bool ok = ta >= 0 && ta < V && tb >= 0 && tb < V;
+      float wa, wb;
+      pair_weights(ta, tb, second.lam[row], wa, wb);
+      const float xt = ok ? wa * ldv<BF16>(logits, base + ta) + wb * ldv<BF16>(logits, base + tb) : 0.f;
+      loss[row] = ok ? (l - (1.f - eps) * xt - eps * (sx / V)) : 0.f;
+    } else {
+      long t = target[row];
+      float xt = (t >= 0 && t < V) ? ldv<BF16>(logits, base + t) : 0.f;
+      loss[row] = (t >= 0 && t < V) ? (l - (1.f - eps) * xt - eps * (sx / V)) : 0.f;
+    }
   }
 }
 
@@ -68,19 +102,32 @@ __global__ void mean_kernel(const float* __restrict__ x, float* __restrict__ out
   if (threadIdx.x == 0) out[0] = red[0] * scale;
 }
 
-template <bool BF16>
+template <bool BF16, class Target>
 __global__ void xent_bwd_kernel(const void* __restrict__ logits, const long* __restrict__ target,
                                 const float* __restrict__ lse, const float* __restrict__ gout, u16* __restrict__ dlogits,
-                                int B, int V, float eps) {
+                                int B, int V, float eps, const Target second) {
   const int row = blockIdx.y;
   const float g = gout[0] / B;
   const float l = lse[row];
   const long t = target[row];
   const long base = (long)row * V;
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < V; j += gridDim.x * blockDim.x) {
-    float p = __expf(ldv<BF16>(logits, base + j) - l);
-    float d = p - eps / V - (j == t ? (1.f - eps) : 0.f);
-    dlogits[base + j] = f2bf(t >= 0 && t < V ? g * d : 0.f);
+  if constexpr (Target::pair) {
+    const long ta = t, tb = second.tb[row];
+    const bool ok = ta >= 0 && ta < V && tb >= 0 && tb < V;
+    float wa, wb;
+    pair_weights(ta, tb, second.lam[row], wa, wb);
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < V; j += gridDim.x * blockDim.x) {
+      float p = __expf(ldv<BF16>(logits, base + j) - l);
+      float c = (j == ta ? wa : 0.f) + (j == tb ? wb : 0.f);
+      float d = p - eps / V - (1.f - eps) * c;
+      dlogits[base + j] = f2bf(ok ? g * d : 0.f);
+    }
+  } else {
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < V; j += gridDim.x * blockDim.x) {
+      float p = __expf(ldv<BF16>(logits, base + j) - l);
+      float d = p - eps / V - (j == t ? (1.f - eps) : 0.f);
+      dlogits[base + j] = f2bf(t >= 0 && t < V ? g * d : 0.f);
+    }
   }
 }
 
@@ -159,9 +206,26 @@ PDT_API int pdt_xent_fwd(const void* logits, int bf16, const long* target, float
                          float* loss_out, int B, int V, float eps, hipStream_t st) {
   dim3 blk(256), grd((B + 3) / 4);
   if (bf16)
-    hipLaunchKernelGGL(xent_fwd_kernel<true>, grd, blk, 0, st, logits, target, lse, loss_rows, B, V, eps);
+    hipLaunchKernelGGL((xent_fwd_kernel<true, Hard>), grd, blk, 0, st, logits, target, lse, loss_rows, B, V, eps,
+                       Hard{});
   else
-    hipLaunchKernelGGL(xent_fwd_kernel<false>, grd, blk, 0, st, logits, target, lse, loss_rows, B, V, eps);
+    hipLaunchKernelGGL((xent_fwd_kernel<false, Hard>), grd, blk, 0, st, logits, target, lse, loss_rows, B, V, eps,
+                       Hard{});
+  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, st, loss_rows, loss_out, B, 1.f / B);
+  PDT_RETURN_LAUNCH();
+}
+
+PDT_API int pdt_xent_pair_fwd(const void* logits, int bf16, const long* ta, const long* tb, const float* lam,
+                              float* lse, float* loss_rows, float* loss_out, int B, int V, float eps,
+                              hipStream_t st) {
+  if (!logits || !ta || !tb || !lam || !lse || !loss_rows || !loss_out || B <= 0 || V <= 0) return -1;
+  dim3 blk(256), grd((B + 3) / 4);
+  const Pair second{tb, lam};
+  if (bf16)
+    hipLaunchKernelGGL((xent_fwd_kernel<true, Pair>), grd, blk, 0, st, logits, ta, lse, loss_rows, B, V, eps, second);
+  else
+    hipLaunchKernelGGL((xent_fwd_kernel<false, Pair>), grd, blk, 0, st, logits, ta, lse, loss_rows, B, V, eps,
+                       second);
   hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, st, loss_rows, loss_out, B, 1.f / B);
   PDT_RETURN_LAUNCH();
 }
@@ -170,10 +234,26 @@ PDT_API int pdt_xent_bwd(const void* logits, int bf16, const long* target, const
                          void* dlogits, int B, int V, float eps, hipStream_t st) {
   dim3 blk(256), grd((V + 255) / 256, B);
   if (bf16)
-    hipLaunchKernelGGL(xent_bwd_kernel<true>, grd, blk, 0, st, logits, target, lse, gout, (u16*)dlogits, B, V, eps);
+    hipLaunchKernelGGL((xent_bwd_kernel<true, Hard>), grd, blk, 0, st, logits, target, lse, gout, (u16*)dlogits, B, V,
+                       eps, Hard{});
   else
-    hipLaunchKernelGGL(xent_bwd_kernel<false>, grd, blk, 0, st, logits, target, lse, gout, (u16*)dlogits, B, V,
-                       eps);
+    hipLaunchKernelGGL((xent_bwd_kernel<false, Hard>), grd, blk, 0, st, logits, target, lse, gout, (u16*)dlogits, B, V,
+                       eps, Hard{});
+  PDT_RETURN_LAUNCH();
+}
+
+PDT_API int pdt_xent_pair_bwd(const void* logits, int bf16, const long* ta, const long* tb, const float* lam,
+                              const float* lse, const float* gout, void* dlogits, int B, int V, float eps,
+                              hipStream_t st) {
+  if (!logits || !ta || !tb || !lam || !lse || !gout || !dlogits || B <= 0 || V <= 0) return -1;
+  dim3 blk(256), grd((V + 255) / 256, B);
+  const Pair second{tb, lam};
+  if (bf16)
+    hipLaunchKernelGGL((xent_bwd_kernel<true, Pair>), grd, blk, 0, st, logits, ta, lse, gout, (u16*)dlogits, B, V, eps,
+                       second);
+  else
+    hipLaunchKernelGGL((xent_bwd_kernel<false, Pair>), grd, blk, 0, st, logits, ta, lse, gout, (u16*)dlogits, B, V,
+                       eps, second);
   PDT_RETURN_LAUNCH();
 }
 

@@ -29,6 +29,20 @@ batch in the zero-padded 4-channel NHWC storage the space-to-depth stem reads in
 The augmentation parameters are counter-based: a sample's crop box and flip are a pure
 function of ``(seed, epoch, global sample index)`` -- independent of world size, batch size
 and the sample's position in the batch.
+
+**Mixup / CutMix** (``mixup_alpha``, ``cutmix_alpha``, ``mix_prob``, ``mix_switch_prob``,
+``mix_mode``; off by default, training only) follow timm's ``Mixup``: the batch is paired with
+its reverse (``partner[b] = B-1-b``), and the partner's *augmented view* (its own crop box and
+flip) is pasted into a rectangle (CutMix) or blended in with weight ``1 - w_own`` (Mixup). The
+blend happens inside the same launch, on the fp32 0..255 values before normalization and the
+single bf16 rounding: there is no second batch buffer and no extra pass. The loader then yields
+``(images, MixedTarget(label_a, label_b, lam))`` -- two labels and one weight per row, what the
+paired-target cross-entropy (``csrc/xent.hip``) consumes; a dense soft-target matrix is never
+built. Unlike the crop boxes, the mix depends on batch composition: the pairing does by
+construction, and the draws (:func:`mix_params`) are keyed by ``(seed, epoch, first global
+sample index of the batch)`` -- reproducible and independent of which thread computes them, but
+not of batch size or world size. Nobody has trained a model to convergence with this recipe
+here; what is tested is that the mixed batch and the loss are the ones the parameters describe.
 """
 from __future__ import annotations
 
@@ -37,6 +51,7 @@ import math
 import queue
 import threading
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -196,6 +211,125 @@ def validate_indices(indices, n):
     return idx
 
 
+# ----------------------------------------------------------------------------- mixing
+class MixedTarget(NamedTuple):
+    """The target of a mixed batch: row ``b`` is ``lam[b]`` of class ``label_a[b]`` and
+    ``1 - lam[b]`` of class ``label_b[b]``. ``label_a`` / ``label_b`` int64 [B], ``lam`` float32
+    [B], on the loader's device. ``fused.softmax_cross_entropy`` takes it in place of labels."""
+    label_a: torch.Tensor
+    label_b: torch.Tensor
+    lam: torch.Tensor
+
+
+_MIX_MODES = ("batch", "elem")
+_M64 = (1 << 64) - 1
+
+
+def check_mix_args(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, mix_mode):
+    """Raise ValueError on a negative alpha, a probability outside [0, 1] or an unknown mode."""
+    for name, v in (("mixup_alpha", mixup_alpha), ("cutmix_alpha", cutmix_alpha)):
+        if not (float(v) >= 0.0) or math.isinf(float(v)):
+            raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+    for name, v in (("mix_prob", mix_prob), ("mix_switch_prob", mix_switch_prob)):
+        if not (0.0 <= float(v) <= 1.0):
+            raise ValueError(f"{name} must lie in [0, 1], got {v!r}")
+    if mix_mode not in _MIX_MODES:
+        raise ValueError(f"mix_mode must be one of {_MIX_MODES}, got {mix_mode!r}")
+
+
+def mix_params(indices, epoch, seed, S, mixup_alpha=0.0, cutmix_alpha=0.0, mix_prob=1.0, mix_switch_prob=0.5,
+               mix_mode="batch"):
+    """Mixup / CutMix parameters of the batch of global sample ``indices`` at output size ``S``
+    (timm's ``Mixup``), as host tensors ``(partner, w_own, rect, lam)``:
+
+    * ``partner`` int64 [B] = ``B-1-b``: the batch is paired with its reverse (the middle element
+      of an odd batch, and a batch of 1, pair with themselves);
+    * ``w_own`` float32 [B]: the weight of the sample's own pixels outside the rectangle;
+    * ``rect`` int32 [B, 4] = ``(y0, x0, y1, x1)``, half-open, output coordinates: the partner's
+      pixels are pasted there (empty when ``y0 == y1`` or ``x0 == x1``);
+    * ``lam`` float32 [B]: the own label's share in the loss.
+
+    With probability ``mix_prob`` a draw mixes (otherwise ``lam = w_own = 1``, empty rectangle);
+    the method is CutMix with probability ``mix_switch_prob`` when both alphas are positive, else
+    whichever alpha is positive; ``lam0 ~ Beta(alpha, alpha)``. Mixup: ``w_own = lam = lam0``.
+    CutMix: a ``int(S sqrt(1 - lam0))``-sided square around a uniform centre, clipped to the
+    image, ``w_own = 1`` and ``lam = 1 - clipped area / S^2``. ``"batch"`` draws once and
+    broadcasts, ``"elem"`` draws per sample.
+
+    A pure function of its arguments: one Philox stream keyed by ``(seed, epoch, indices[0])``,
+    drawn vectorised in a fixed order."""
+    check_mix_args(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, mix_mode)
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    B, S = int(idx.size), int(S)
+    if B == 0 or S <= 0:
+        raise ValueError("mix_params needs a non-empty batch and S >= 1")
+    ma, ca = float(mixup_alpha), float(cutmix_alpha)
+    key = [int(seed) & _M64, ((int(epoch) & _M32) << 32) | (int(idx[0]) & _M32)]
+    rng = np.random.Generator(np.random.Philox(key=key))
+    n = 1 if mix_mode == "batch" else B
+    u_mix, u_switch = rng.random(n), rng.random(n)
+    lam_mixup = rng.beta(ma, ma, n) if ma > 0 else np.ones(n)
+    lam_cut = rng.beta(ca, ca, n) if ca > 0 else np.ones(n)
+    cy, cx = rng.integers(0, S, n), rng.integers(0, S, n)
+
+    mixes = (u_mix < float(mix_prob)) & ((ma > 0) | (ca > 0))
+    cut = (u_switch < float(mix_switch_prob)) if (ma > 0 and ca > 0) else np.full(n, ca > 0)
+    cut = cut & mixes
+    mixup = mixes & ~cut
+    side = (S * np.sqrt(1.0 - lam_cut)).astype(np.int64)  # ch = cw = int(S r)
+    half = side // 2
+    y0, y1 = np.clip(cy - half, 0, S), np.clip(cy + half, 0, S)
+    x0, x1 = np.clip(cx - half, 0, S), np.clip(cx + half, 0, S)
+    rect = np.where(cut[:, None], np.stack([y0, x0, y1, x1], axis=1), 0).astype(np.int32)
+    area = (rect[:, 2] - rect[:, 0]).astype(np.int64) * (rect[:, 3] - rect[:, 1])
+    lam = np.where(cut, 1.0 - area / float(S * S), np.where(mixup, lam_mixup, 1.0)).astype(np.float32)
+    w_own = np.where(mixup, lam_mixup, 1.0).astype(np.float32)
+    if n != B:
+        rect, lam, w_own = np.repeat(rect, B, axis=0), np.repeat(lam, B), np.repeat(w_own, B)
+    partner = np.arange(B - 1, -1, -1, dtype=np.int64)
+    return (torch.from_numpy(partner), torch.from_numpy(np.ascontiguousarray(w_own)),
+            torch.from_numpy(np.ascontiguousarray(rect)), torch.from_numpy(np.ascontiguousarray(lam)))
+
+
+def validate_mix(partner, w_own, rect, lam, S):
+    """Raise unless every rectangle lies inside ``[0, S]^2`` with ``y0 <= y1`` and ``x0 <= x1``,
+    ``0 <= w_own <= 1``, ``0 <= lam <= 1`` and every partner lies in ``[0, B)`` (the kernel
+    trusts what it is given)."""
+    B = int(partner.shape[0])
+    if tuple(rect.shape) != (B, 4) or tuple(w_own.shape) != (B,) or tuple(lam.shape) != (B,):
+        raise ValueError(f"mix parameters of a batch of {B}: shapes {tuple(w_own.shape)}, {tuple(rect.shape)}, "
+                         f"{tuple(lam.shape)}")
+    r = rect.to(torch.int64)
+    bad = (r[:, 0] < 0) | (r[:, 1] < 0) | (r[:, 2] > S) | (r[:, 3] > S) | (r[:, 0] > r[:, 2]) | (r[:, 1] > r[:, 3])
+    if bool(bad.any()):
+        i = int(torch.nonzero(bad)[0])
+        raise ValueError(f"cut rectangle {rect[i].tolist()} of batch entry {i} is outside the {S}x{S} output")
+    for name, v in (("w_own", w_own), ("lam", lam)):
+        bad = ~((v >= 0) & (v <= 1))  # NaN is bad too
+        if bool(bad.any()):
+            i = int(torch.nonzero(bad)[0])
+            raise ValueError(f"{name} = {float(v[i])} of batch entry {i} is outside [0, 1]")
+    bad = (partner < 0) | (partner >= B)
+    if bool(bad.any()):
+        i = int(torch.nonzero(bad)[0])
+        raise ValueError(f"partner {int(partner[i])} of batch entry {i} is outside the batch of {B}")
+
+
+def mix_images_torch(x, partner, w_own, rect):
+    """The mix in torch on normalized fp32 views ``x`` [B, 3, S, S]: Mixup's blend
+    ``w x + (1 - w) x[partner]`` outside the rectangle, the partner's pixels inside it."""
+    B, _, S, _ = x.shape
+    xp = x[partner]
+    w = w_own.to(torch.float32).view(B, 1, 1, 1)
+    out = torch.where(w == 1, x, w * x + (1 - w) * xp)
+    yy = torch.arange(S).view(1, S, 1)
+    xx = torch.arange(S).view(1, 1, S)
+    r = rect.to(torch.int64)
+    inside = ((yy >= r[:, 0].view(B, 1, 1)) & (yy < r[:, 2].view(B, 1, 1))
+              & (xx >= r[:, 1].view(B, 1, 1)) & (xx < r[:, 3].view(B, 1, 1)))
+    return torch.where(inside[:, None], xp, out)
+
+
 def crop_resize_normalize_torch(images, box, S, mean, std, dtype=torch.float32):
     """The kernel's math in torch: ``images`` uint8 [B, Hs, Ws, 3] -> [B, 3, S, S] ``dtype``
     (computed in fp32): per-sample crop, bilinear ``F.interpolate`` (``align_corners=False``, no
@@ -216,7 +350,9 @@ def crop_resize_normalize_torch(images, box, S, mean, std, dtype=torch.float32):
 class PackedImageLoader:
     """Config-facing loader over a packed image set (see the module docstring).
 
-    Yields ``(images [B, 3, S, S], labels int64 [B])`` on ``device``. On the native path
+    Yields ``(images [B, 3, S, S], labels int64 [B])`` on ``device`` -- with Mixup / CutMix
+    switched on (``mixup_alpha`` / ``cutmix_alpha`` > 0 and ``training``), ``(images,
+    MixedTarget)``. On the native path
     (CUDA device, kernel library present, bf16, ``channels_last``) ``images`` is a view into
     bf16 ``[B, S, S, 4]`` tagged ``pdt_nhwc_pad = 4``; otherwise the torch path returns
     ``dtype`` (``channels_last`` strides when asked).
@@ -229,7 +365,9 @@ class PackedImageLoader:
     def __init__(self, data_dir, batch_size, training=True, image_size=224, shuffle=True, seed=0,
                  scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), hflip=0.5, crop_fraction=0.875, mean=None, std=None,
                  resident="auto", resident_limit_gb=16, prefetch=2, dtype=None, channels_last=True, device=None,
-                 num_workers=0):
+                 num_workers=0, mixup_alpha=0.0, cutmix_alpha=0.0, mix_prob=1.0, mix_switch_prob=0.5,
+                 mix_mode="batch"):
+        check_mix_args(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, mix_mode)
         self.dataset = open_packed(data_dir)
         ds = self.dataset
         self.batch_size = int(batch_size)
@@ -238,6 +376,10 @@ class PackedImageLoader:
         self.seed = int(seed)
         self.scale, self.ratio, self.hflip = tuple(scale), tuple(ratio), float(hflip)
         self.crop_fraction = float(crop_fraction)
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        self.mix_prob, self.mix_switch_prob, self.mix_mode = float(mix_prob), float(mix_switch_prob), mix_mode
+        # samples are mixed in training only, and only when a method is switched on
+        self.mixing = bool(training) and (self.mixup_alpha > 0 or self.cutmix_alpha > 0)
         self.mean = tuple(mean) if mean is not None else (ds.mean or IMAGENET_MEAN)
         self.std = tuple(std) if std is not None else (ds.std or IMAGENET_STD)
         assert len(self.mean) == 3 and len(self.std) == 3 and all(s > 0 for s in self.std)
@@ -301,6 +443,17 @@ class PackedImageLoader:
         validate_boxes(box, Hs, Ws)
         return box
 
+    def mix(self, indices, epoch=None):
+        """The validated mix parameters ``(partner, w_own, rect, lam)`` (host) of the batch of
+        global sample ``indices`` in ``epoch`` (default: the current one); None when the loader
+        does not mix."""
+        if not self.mixing:
+            return None
+        m = mix_params(indices, self.epoch if epoch is None else epoch, self.seed, self.image_size,
+                       self.mixup_alpha, self.cutmix_alpha, self.mix_prob, self.mix_switch_prob, self.mix_mode)
+        validate_mix(*m, self.image_size)
+        return m
+
     def __iter__(self):
         if self.mode == "torch":
             return self._iter_torch()
@@ -319,10 +472,18 @@ class PackedImageLoader:
             order = np.argsort(idx, kind="stable")
             imgs = np.empty((len(idx),) + ds.images.shape[1:], dtype=np.uint8)
             imgs[order] = ds.images[idx[order]]
-            x = crop_resize_normalize_torch(torch.from_numpy(imgs), box, self.image_size, self.mean, self.std,
-                                            self.dtype)
+            mix = self.mix(indices, epoch)
             y = torch.from_numpy(ds.labels[idx])
-            yield x.contiguous(memory_format=fmt).to(self.device), y.to(self.device)
+            if mix is None:
+                x = crop_resize_normalize_torch(torch.from_numpy(imgs), box, self.image_size, self.mean, self.std,
+                                                self.dtype)
+                yield x.contiguous(memory_format=fmt).to(self.device), y.to(self.device)
+                continue
+            partner, w_own, rect, lam = mix
+            x = crop_resize_normalize_torch(torch.from_numpy(imgs), box, self.image_size, self.mean, self.std)
+            x = mix_images_torch(x, partner, w_own, rect).to(self.dtype)  # blend and paste in fp32
+            target = MixedTarget(y.to(self.device), y[partner].to(self.device), lam.to(self.device))
+            yield x.contiguous(memory_format=fmt).to(self.device), target
 
     # ------------------------------------------------------------------ native paths
     def _upload_params(self, kidx, labels, box):
@@ -336,11 +497,45 @@ class PackedImageLoader:
         dev = host.to(self.device, non_blocking=True)
         return dev[:2 * B].view(torch.int64), dev[2 * B:4 * B].view(torch.int64), dev[4 * B:].view(B, 5)
 
-    def _launch(self, src, kidx, box):
+    def _upload_mixed(self, kidx, labels, box, mix):
+        """:meth:`_upload_params` of a mixed batch, still one pinned buffer and one H2D copy: the
+        gather indices, labels and boxes of the samples and of their partners (``kidx[partner]``:
+        in staged mode the partner is read from the same staging slot), the rectangles, ``w_own``
+        and ``lam``. Returns ``(kidx, box, pidx, pbox, rect, w_own)`` and the MixedTarget."""
+        partner, w_own, rect, lam = mix
+        B = len(kidx)
+        kidx = torch.from_numpy(np.ascontiguousarray(kidx, dtype=np.int64))
+        labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int64))
+        host = torch.empty(24 * B, dtype=torch.int32, pin_memory=True)
+        i64 = host[:8 * B].view(torch.int64).view(4, B)  # the int64 vectors first: 8-byte aligned for any B
+        i64[0], i64[1], i64[2], i64[3] = kidx, labels, kidx[partner], labels[partner]
+        host[8 * B:13 * B].view(B, 5).copy_(box)
+        host[13 * B:18 * B].view(B, 5).copy_(box[partner])
+        host[18 * B:22 * B].view(B, 4).copy_(rect)
+        host[22 * B:23 * B].view(torch.float32).copy_(w_own)
+        host[23 * B:].view(torch.float32).copy_(lam)
+        dev = host.to(self.device, non_blocking=True)
+        d64 = dev[:8 * B].view(torch.int64).view(4, B)
+        args = (d64[0], dev[8 * B:13 * B].view(B, 5), d64[2], dev[13 * B:18 * B].view(B, 5),
+                dev[18 * B:22 * B].view(B, 4), dev[22 * B:23 * B].view(torch.float32))
+        return args, MixedTarget(d64[1], d64[3], dev[23 * B:].view(torch.float32))
+
+    def _batch(self, src, kidx, labels, box, mix):
+        """Upload one batch's parameters and launch: ``(images, labels or MixedTarget)``."""
+        if mix is None:
+            kidx_d, y, box_d = self._upload_params(kidx, labels, box)
+            return self._launch(src, kidx_d, box_d), y
+        (kidx_d, box_d, *mixed), target = self._upload_mixed(kidx, labels, box, mix)
+        return self._launch(src, kidx_d, box_d, mixed), target
+
+    def _launch(self, src, kidx, box, mixed=None):
         from ..ops import native_ops
         B, S = box.shape[0], self.image_size
         buf = torch.empty((B, S, S, 4), dtype=torch.bfloat16, device=self.device)
-        native_ops.crop_resize_normalize(src, kidx, box, buf, self.mean, self.std)
+        if mixed is None:
+            native_ops.crop_resize_normalize(src, kidx, box, buf, self.mean, self.std)
+        else:
+            native_ops.crop_resize_normalize_mix(src, kidx, box, *mixed, buf, self.mean, self.std)
         x = buf[..., :3].permute(0, 3, 1, 2)
         x.pdt_nhwc_pad = 4
         return x
@@ -361,8 +556,7 @@ class PackedImageLoader:
         epoch = self.epoch
         for indices in self._index_batches():
             idx = validate_indices(indices, len(ds))
-            kidx, y, box = self._upload_params(idx, ds.labels[idx], self.boxes(indices, epoch))
-            yield self._launch(src, kidx, box), y
+            yield self._batch(src, idx, ds.labels[idx], self.boxes(indices, epoch), self.mix(indices, epoch))
 
     def _staging_ring(self):
         if self._ring is None:
@@ -422,6 +616,7 @@ class PackedImageLoader:
                         copied[slot].synchronize()
                     idx = validate_indices(indices, len(ds))
                     box = self.boxes(indices, epoch)
+                    mix = self.mix(indices, epoch)
                     order = np.argsort(idx, kind="stable")
                     B = len(idx)
                     np.take(ds.images, idx[order], axis=0, out=pinned[:B].numpy())
@@ -432,7 +627,7 @@ class PackedImageLoader:
                         ev = torch.cuda.Event()
                         ev.record(side)
                     copied[slot] = ev
-                    if not put(("batch", slot, B, kidx, ds.labels[idx], box, ev)):
+                    if not put(("batch", slot, B, kidx, ds.labels[idx], box, mix, ev)):
                         return
                 put(("end",))
             except BaseException as e:  # re-raised in the consumer
@@ -448,11 +643,10 @@ class PackedImageLoader:
                     break
                 if item[0] == "error":
                     raise item[1]
-                _, slot, B, kidx, labels, box, ev = item
+                _, slot, B, kidx, labels, box, mix, ev = item
                 cur = torch.cuda.current_stream(self.device)
                 cur.wait_event(ev)
-                kidx_d, y, box_d = self._upload_params(kidx, labels, box)
-                x = self._launch(ring[slot][1], kidx_d, box_d)
+                x, y = self._batch(ring[slot][1], kidx, labels, box, mix)
                 rel = torch.cuda.Event()
                 rel.record(cur)
                 release_ev[slot] = rel

@@ -250,7 +250,21 @@ def embed_tokens(tok, cls_token, pos_embed):
 
 
 def softmax_cross_entropy(logits, target, label_smoothing: float = 0.0):
-    """Mean softmax cross-entropy (fused fwd/bwd kernel on the native path)."""
+    """Mean softmax cross-entropy (fused fwd/bwd kernel on the native path). ``target``: int64
+    labels [B], or a mixed batch's ``(label_a, label_b, lam)`` (``data.MixedTarget``): row ``b``
+    is ``lam[b]`` of class ``label_a[b]`` and ``1 - lam[b]`` of class ``label_b[b]``."""
+    if isinstance(target, tuple):
+        label_a, label_b, lam = target
+        if _use_native(logits):
+            from . import native_ops
+            if logits.dim() == 2:
+                return native_ops.softmax_cross_entropy_pair(logits, label_a, label_b, lam, label_smoothing)
+            native_ops.fallback("softmax_cross_entropy", f"logits of shape {tuple(logits.shape)} (kernel: [B, V])")
+        x = logits.float()
+        ce_a = F.cross_entropy(x, label_a, label_smoothing=label_smoothing, reduction="none")
+        ce_b = F.cross_entropy(x, label_b, label_smoothing=label_smoothing, reduction="none")
+        lam = lam.to(torch.float32)
+        return (lam * ce_a + (1 - lam) * ce_b).mean()
     if _use_native(logits):
         from . import native_ops
         return native_ops.softmax_cross_entropy(logits, target, label_smoothing)

@@ -592,6 +592,44 @@ def crop_resize_normalize(src, idx, box, out, mean, std):
                                               ctypes.addressof(m), ctypes.addressof(inv), _s()), "crop_resize_norm")
 
 
+def crop_resize_normalize_mix(src, idx, box, pidx, pbox, rect, w_own, out, mean, std):
+    """:func:`crop_resize_normalize` with Mixup / CutMix in the same launch: output ``b`` is mixed
+    with its partner's augmented view -- the crop ``pbox[b]`` (the partner's own box and flip) of
+    stored image ``pidx[b]``. Inside the rectangle ``rect[b] = (y0, x0, y1, x1)`` (half-open,
+    output coordinates; empty when ``y0 == y1`` or ``x0 == x1``) a pixel is the partner's; outside
+    it is the own one when ``w_own[b] == 1``, else ``w_own * own + (1 - w_own) * partner``, formed
+    in fp32 before the normalization and the one rounding to bf16.
+
+    ``pidx`` int64 [B]; ``pbox`` int32 [B, 5]; ``rect`` int32 [B, 4] inside ``[0, S]^2``; ``w_own``
+    float32 [B] in [0, 1]; the rest as in :func:`crop_resize_normalize`. The kernel trusts them
+    all: validate on the host (``data/packed.py``: ``validate_boxes``, ``validate_mix``)."""
+    assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and src.is_contiguous()
+    assert out.dtype == torch.bfloat16 and out.dim() == 4 and out.is_contiguous() and out.device == src.device
+    B, S, S2, Cp = out.shape
+    assert S == S2 and Cp % 4 == 0 and B > 0
+    assert box.dtype == torch.int32 and tuple(box.shape) == (B, 5) and box.is_contiguous() and box.device == src.device
+    if idx is not None:
+        assert idx.dtype == torch.int64 and tuple(idx.shape) == (B,) and idx.is_contiguous() \
+            and idx.device == src.device
+    else:
+        assert src.shape[0] >= B
+    assert pidx is not None and pidx.dtype == torch.int64 and tuple(pidx.shape) == (B,) and pidx.is_contiguous() \
+        and pidx.device == src.device
+    assert pbox.dtype == torch.int32 and tuple(pbox.shape) == (B, 5) and pbox.is_contiguous() \
+        and pbox.device == src.device
+    assert rect.dtype == torch.int32 and tuple(rect.shape) == (B, 4) and rect.is_contiguous() \
+        and rect.device == src.device
+    assert w_own.dtype == torch.float32 and tuple(w_own.shape) == (B,) and w_own.is_contiguous() \
+        and w_own.device == src.device
+    assert len(mean) == 3 and len(std) == 3 and all(float(s) > 0 for s in std)
+    m = (c_float * 3)(*[float(v) for v in mean])
+    inv = (c_float * 3)(*[1.0 / float(v) for v in std])
+    n, Hs, Ws, _ = src.shape
+    _chk(_load().pdt_crop_resize_norm_mix_u8_bf16(_p(src), Hs, Ws, _p(idx), _p(box), _p(pidx), _p(pbox), _p(rect),
+                                                  _p(w_own), _p(out), B, S, Cp, ctypes.addressof(m),
+                                                  ctypes.addressof(inv), _s()), "crop_resize_norm_mix")
+
+
 def synthetic_images(shape, dtype, device, seed=0, channels_last=True):
     n, c, h, w = shape
     if channels_last:
@@ -2864,6 +2902,49 @@ class _XEnt(torch.autograd.Function):
         _chk(_load().pdt_xent_bwd(_p(logits), int(logits.dtype == torch.bfloat16), _p(target), _p(lse), _p(g),
                                   _p(dl), B, V, float(ctx.eps), _s()), "xent_bwd")
         return dl, None, None
+
+
+class _XEntPair(torch.autograd.Function):
+    """Cross-entropy against paired targets (``pdt_xent_pair_fwd`` / ``_bwd``): row ``b`` is
+    ``lam[b]`` of class ``ta[b]`` and ``1 - lam[b]`` of class ``tb[b]``."""
+
+    @staticmethod
+    def forward(ctx, logits, ta, tb, lam, eps):
+        lib = _load()
+        logits = logits.contiguous()
+        B, V = logits.shape
+        is_bf16 = logits.dtype == torch.bfloat16
+        if not is_bf16 and logits.dtype != torch.float32:
+            logits = logits.float()
+        ta, tb = ta.to(torch.long).contiguous(), tb.to(torch.long).contiguous()
+        lam = lam.to(torch.float32).contiguous()
+        assert ta.numel() == B and tb.numel() == B and lam.numel() == B
+        assert ta.device == logits.device and tb.device == logits.device and lam.device == logits.device
+        lse = torch.empty(B, dtype=torch.float32, device=logits.device)
+        rows = torch.empty(B, dtype=torch.float32, device=logits.device)
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        _chk(lib.pdt_xent_pair_fwd(_p(logits), int(is_bf16), _p(ta), _p(tb), _p(lam), _p(lse), _p(rows), _p(loss), B,
+                                   V, float(eps), _s()), "xent_pair_fwd")
+        ctx.save_for_backward(logits, ta, tb, lam, lse)
+        ctx.eps = eps
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, ta, tb, lam, lse = ctx.saved_tensors
+        B, V = logits.shape
+        g = g.float().reshape(1).contiguous()
+        dl = torch.empty((B, V), dtype=torch.bfloat16, device=logits.device)
+        _chk(_load().pdt_xent_pair_bwd(_p(logits), int(logits.dtype == torch.bfloat16), _p(ta), _p(tb), _p(lam),
+                                       _p(lse), _p(g), _p(dl), B, V, float(ctx.eps), _s()), "xent_pair_bwd")
+        return dl, None, None, None, None
+
+
+def softmax_cross_entropy_pair(logits, label_a, label_b, lam, label_smoothing=0.0):
+    """Mean cross-entropy of [B, V] ``logits`` against ``lam * onehot(label_a) + (1 - lam) *
+    onehot(label_b)`` (label-smoothed), without building that matrix."""
+    assert logits.dim() == 2
+    return _XEntPair.apply(logits, label_a, label_b, lam, float(label_smoothing))
 
 
 def softmax_cross_entropy(logits, target, label_smoothing=0.0):

@@ -25,7 +25,8 @@ MI355X-first changes to the hot loop:
     stats over the first 10 iterations) the whole step -- zero_grad, forward, loss,
     backward with DDP's RCCL all-reduces, the fused optimizer -- is captured once as a
     HIP graph and replayed for every later full-size batch (copied into the graph's
-    static input buffers); the optimizer is capturable, so replays use the scheduler's
+    static input buffers -- the images and the target, which is the labels or, for a mixed
+    batch, the three tensors of a ``MixedTarget``); the optimizer is capturable, so replays use the scheduler's
     current lr and Adam's current step. Partial batches and validation run eagerly.
 """
 from __future__ import annotations
@@ -42,6 +43,19 @@ from ..utils.profiling import PhaseTimer
 
 
 GRAPH_WARMUP = 11  # eager steps before the capture (DDP's runtime statistics cover iterations 1..10)
+
+
+def _map_target(fn, target):
+    """``fn`` over a target: one tensor (labels), or a tuple of tensors (a mixed batch's
+    ``MixedTarget``), which keeps its type."""
+    if torch.is_tensor(target):
+        return fn(target)
+    vals = [fn(t) for t in target]
+    return type(target)(*vals) if hasattr(target, "_fields") else type(target)(vals)
+
+
+def _target_shapes(target):
+    return [target.shape] if torch.is_tensor(target) else [t.shape for t in target]
 
 
 class _LossCurve:
@@ -144,7 +158,7 @@ class Trainer(BaseTrainer):
         # native stem reads in place: re-laying it out would copy it and drop the tag
         if self.channels_last and data.dim() == 4 and getattr(data, "pdt_nhwc_pad", None) is None:
             data = data.contiguous(memory_format=torch.channels_last)
-        return data, target.to(self.device, non_blocking=True)
+        return data, _map_target(lambda t: t.to(self.device, non_blocking=True), target)
 
     def _autocast(self):
         if self.autocast_dtype is None:
@@ -266,9 +280,14 @@ class Trainer(BaseTrainer):
                 self._capture(data, target)
             cur.wait_stream(side)
         io = self._graph_io
-        if self._graph is not None and io[0].shape == data.shape and io[1].shape == target.shape:
+        if self._graph is not None and io[0].shape == data.shape \
+                and type(io[1]) is type(target) and _target_shapes(io[1]) == _target_shapes(target):
             io[0].copy_(data)
-            io[1].copy_(target)
+            if torch.is_tensor(target):
+                io[1].copy_(target)
+            else:  # a mixed batch: every target tensor is a static graph input
+                for static, t in zip(io[1], target):
+                    static.copy_(t)
             self.optimizer.refresh_scalars()  # the scheduler's lr (written outside the graph)
             self._graph.replay()
             return io[2]
@@ -287,7 +306,7 @@ class Trainer(BaseTrainer):
             buf = nhwc_padded_view(data, cp).clone(memory_format=torch.channels_last)
             gx = buf[:, :data.shape[1]]
             gx.pdt_nhwc_pad = cp
-        gy = target.clone()
+        gy = _map_target(torch.clone, target)
         self.optimizer.refresh_scalars()
         # the eager warm-up's cached activation blocks go back first (the graph gets a private
         # pool: both reserved at once would double the activation memory)

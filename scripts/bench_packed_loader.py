@@ -13,6 +13,11 @@ profiles/packed_loader.txt).
 3. ResNet-50 bf16 training steps/s through Trainer with PackedImageLoader (resident) against
    SyntheticImageNetLoader: 20 timed steps after a warm-up epoch, two runs each.
 
+4. ``--mix``: the launch with Mixup / CutMix (pdt_crop_resize_norm_mix_u8_bf16) -- no mixing,
+   all-CutMix, all-Mixup -- against the plain entry point, three rounds of each for the run-to-run
+   spread; and with training, ResNet-50 steps/s with a mixing loader against the same loader
+   without mixing.
+
 A run without a GPU fails: nothing here falls back to the CPU.
 """
 import argparse
@@ -100,6 +105,72 @@ def bench_kernel(B, dev):
     gi = torch.arange(B, dtype=torch.int64, device=dev)
     t_syn = event_ms(lambda: native_ops.synthetic_images_at(out, gi, 3, 1, y, 1000))
     print(f"pdt_synth_images_bf16 at the same batch: {t_syn:.3f} ms (crop_resize_norm / synth = {t / t_syn:.2f}x)")
+
+
+def bench_mix_kernel(B, dev):
+    print(f"== mixing launch: B={B}, 256x256x3 uint8 store -> 224x224x4 bf16, RandomResizedCrop boxes, partner = "
+          "the reversed batch")
+    from pytorch_distributed_template_amd.data import mix_params
+    Hs = Ws = 256
+    S = 224
+    n_src = min(B, 4096)
+    src = torch.randint(0, 256, (n_src, Hs, Ws, 3), dtype=torch.uint8, device=dev)
+    idx = (torch.randperm(B, device=dev) % n_src).to(torch.int64)
+    box = random_resized_crop_boxes(torch.arange(B), 0, 0, Hs, Ws).to(dev)
+    pidx, pbox = idx.flip(0).contiguous(), box.flip(0).contiguous()
+    out = torch.empty((B, S, S, 4), dtype=torch.bfloat16, device=dev)
+    variants = {"plain entry point": None}
+    for name, kw in (("mix entry point, no mixing", dict(mixup_alpha=0.8, cutmix_alpha=1.0, mix_prob=0.0)),
+                     ("all CutMix (alpha 1.0)", dict(cutmix_alpha=1.0)), ("all Mixup (alpha 0.8)", dict(mixup_alpha=0.8))):
+        _, w_own, rect, _ = mix_params(list(range(B)), 0, 0, S, mix_mode="elem", **kw)
+        variants[name] = (rect.to(dev), w_own.to(dev))
+    times = {k: [] for k in variants}
+    for _ in range(3):
+        for name, v in variants.items():
+            if v is None:
+                fn = lambda: native_ops.crop_resize_normalize(src, idx, box, out, MEAN, STD)  # noqa: E731
+            else:
+                fn = lambda v=v: native_ops.crop_resize_normalize_mix(src, idx, box, pidx, pbox, v[0], v[1], out,  # noqa: E731
+                                                                      MEAN, STD)
+            times[name].append(event_ms(fn))
+    base = min(times["plain entry point"])
+    for name, t in times.items():
+        print(f"{name:28s}: " + ", ".join(f"{x:.3f}" for x in t) + f" ms   (best / plain best = {min(t) / base:.2f}x)")
+
+
+def bench_train_mix(data_dir, batch, dev):
+    from pytorch_distributed_template_amd.config import ConfigParser
+    from pytorch_distributed_template_amd.ops import fused
+    from pytorch_distributed_template_amd.runtime import (autocast_dtype, build_criterion_metrics, build_loader,
+                                                          build_model, build_optimizer)
+    from pytorch_distributed_template_amd.trainer import Trainer
+    print(f"== ResNet-50 bf16 native through Trainer, batch {batch}, label smoothing: PackedImageLoader with and "
+          "without Mixup 0.8 / CutMix 1.0; 20 timed steps after a warm-up epoch")
+    save = tempfile.mkdtemp(prefix="pdt_bench_")
+    for run in (1, 2):
+        for name, mix in (("no mixing", {}), ("mixup+cutmix", dict(mixup_alpha=0.8, cutmix_alpha=1.0))):
+            cfg = json.loads((ROOT / "config" / "resnet50_bf16_packed.json").read_text())
+            cfg["train_loader"]["args"].update(data_dir=str(data_dir), batch_size=batch, resident=True, **mix)
+            cfg["trainer"].update(save_dir=save, verbosity=0)
+            config = ConfigParser(cfg, run_id=f"mix{run}{len(mix)}")
+            model = build_model(config, dev)
+            criterion, metrics = build_criterion_metrics(config)
+            optimizer, sched = build_optimizer(config, model)
+            loader = build_loader(config, "train_loader")
+            tr = Trainer(model, criterion, metrics, optimizer, config=config, device=dev, data_loader=loader,
+                         valid_data_loader=None, lr_scheduler=sched, len_epoch=6,
+                         autocast_dtype=autocast_dtype(config, dev), channels_last=True)
+            tr._train_epoch(1)
+            tr.len_epoch = 20
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            log = tr._train_epoch(2)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            print(f"run {run} {name:14s}: {20 / dt:.3f} steps/s  {20 * batch / dt:,.0f} img/s  loss {log['loss']:.3f}")
+            del tr, model, optimizer, loader
+            torch.cuda.empty_cache()
+    fused.set_backend("auto")
 
 
 def bench_feed(data_dir, B, dev):
@@ -191,6 +262,7 @@ def main():
     ap.add_argument("--data-dir", default=None, help="an existing packed set (default: generate one)")
     ap.add_argument("--skip-train", action="store_true")
     ap.add_argument("--skip-feed", action="store_true")
+    ap.add_argument("--mix", action="store_true", help="measure the Mixup / CutMix launch and training with it instead")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_packed_loader.py needs a GPU")
@@ -198,6 +270,15 @@ def main():
     dev = torch.device("cuda", torch.cuda.current_device())
     print(f"device: {torch.cuda.get_device_name(dev)}; torch {torch.__version__}; host CPUs used: "
           f"{os.environ.get('OMP_NUM_THREADS', 'all')}")
+    if a.mix:
+        bench_mix_kernel(a.batch, dev)
+        if not a.skip_train:
+            with tempfile.TemporaryDirectory(prefix="pdt_packed_") as tmp:
+                data_dir = Path(a.data_dir) if a.data_dir else Path(tmp) / "set"
+                if not a.data_dir:
+                    make_set(data_dir, a.n)
+                bench_train_mix(data_dir, a.train_batch, dev)
+        return
     bench_kernel(a.batch, dev)
     if a.skip_feed and a.skip_train:
         return
