@@ -10,7 +10,8 @@
 //
 // The conversions are the gfx950 packed converts v_cvt_pk_fp8_f32 /
 // v_cvt_pk_bf8_f32 (round to nearest even); inputs are clamped to the format's
-// finite range first, so nothing overflows to NaN.
+// finite range first, so nothing overflows to NaN. A NaN input gets the -FMAX code (the clamp
+// is fminf(fmaxf(NaN, -FMAX), FMAX)) and is left out of the amax (fmaxf drops it).
 #include <cstdlib>
 #include <mutex>
 

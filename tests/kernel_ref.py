@@ -1,10 +1,11 @@
 """Float64 references, error metrics, guard-banded buffers and input families for the element
-and row kernels (csrc/bn_act.hip, pool.hip, layernorm.hip, xent.hip).
+and row kernels (csrc/bn_act.hip, pool.hip, layernorm.hip, xent.hip), and a bit-exact numpy float32
+mirror of the fp8 casts and their scaling state (csrc/fp8.hip; last section).
 
 Used by tests/test_kernel_ref_cpu.py (which checks this module against PyTorch's float64 CPU ops
 and against seeded faults) and by the GPU tests test_bn_act_kernels_gpu.py,
-test_pool_kernels_gpu.py and test_row_kernels_gpu.py. A plain module: no fixtures, no pytest
-settings.
+test_pool_kernels_gpu.py, test_row_kernels_gpu.py and test_fp8_cast_kernels_gpu.py. A plain
+module: no fixtures, no pytest settings.
 
 Every reference is a formula on float64 tensors (the fp32 op is never called and upcast). Every
 reference that feeds a bounded comparison also returns ``abs_terms``: the sum of the absolute
@@ -31,6 +32,7 @@ Bounds (U = 2^-24, the unit roundoff of fp32)
 """
 import math
 
+import numpy as np
 import torch
 
 U = 2.0 ** -24          # fp32 unit roundoff
@@ -354,6 +356,12 @@ def ln_bwd_ref(dy, x, g, mean, rstd, addend=None, dg0=None, db0=None):
 GELU_C = math.sqrt(2.0 / math.pi)
 
 
+def gelu_tanh_ref(z):
+    """0.5 z (1 + tanh(u)), u = sqrt(2/pi) (z + 0.044715 z^3)."""
+    z = f64(z)
+    return 0.5 * z * (1 + torch.tanh(GELU_C * (z + 0.044715 * z ** 3)))
+
+
 def gelu_tanh_grad_ref(z):
     """d/dz [0.5 z (1 + tanh(u))], u = sqrt(2/pi) (z + 0.044715 z^3)."""
     z = f64(z)
@@ -413,3 +421,295 @@ def exact_ln_bwd_inputs(rows, D, g):
     return dict(dy=ints((rows, D), g), x=ints((rows, D), g), addend=ints((rows, D), g),
                 gamma=pow2((D,), g, -1, 1), mean=ints((rows,), g, -2, 2, dtype=torch.float32),
                 rstd=torch.exp2(-ints((rows,), g, 0, 1, dtype=torch.float32)))
+
+
+# ------------------------------------------------------------------------- fp8 quantization
+# csrc/fp8.hip, mirrored operation by operation in numpy float32: one correctly rounded divide
+# (scale = FMAX / amax), one multiply (x * scale), the clamp to +-FMAX and one round to nearest
+# even. Each of these is a single IEEE operation, so the mirror is exact and the GPU tests compare
+# codes, dq, partials and the scaling state with equality. No library fp8 cast is used here:
+# fp8_encode works on the bits of the float32 pattern, fp8_decode from the format's formula.
+FP8_FMAX = (448.0, 57344.0)      # fmt 0 = OCP e4m3fn (no infinity), 1 = OCP e5m2
+FP8_MAX_CODE = (0x7E, 0x7B)
+_FP8_MBITS = (3, 2)
+_FP8_EMIN = (-6, -14)            # exponent of the smallest normal
+FP8_META_WORDS = 21
+FP8_HIST = 16
+
+
+def _np32(x):
+    """float32 numpy array of a tensor (any device, bf16 or fp32), an array or a scalar."""
+    if torch.is_tensor(x):
+        x = x.detach().to(torch.float32).cpu().numpy()
+    return np.ascontiguousarray(np.asarray(x, dtype=np.float32))
+
+
+def fp8_encode(v32, fmt):
+    """float32 array -> uint8 OCP fp8 codes: fminf(fmaxf(v, -FMAX), FMAX), then round to nearest
+    even (into the subnormal range too), the sign of zero kept. NaN goes where that clamp sends it:
+    fmaxf(NaN, -FMAX) = -FMAX, so to the -FMAX code whatever its sign bit."""
+    v32 = _np32(v32)
+    M, emin = _FP8_MBITS[fmt], _FP8_EMIN[fmt]
+    bits = v32.view(np.uint32).astype(np.uint64)
+    sign = (bits >> np.uint64(31)) << np.uint64(7)
+    mag = bits & np.uint64(0x7FFFFFFF)
+    nan = mag > np.uint64(0x7F800000)
+    fmax_bits = np.uint64(np.array(FP8_FMAX[fmt], dtype=np.float32).view(np.uint32))
+    mag = np.minimum(mag, fmax_bits)                      # the clamp (infinity included)
+    e = (mag >> np.uint64(23)).astype(np.int64) - 127     # (fp32 subnormals: e = -127, far below half
+    sig = (mag & np.uint64(0x7FFFFF)) | np.uint64(1 << 23)  # the smallest code, they round to 0)
+    et = np.maximum(e, emin)                              # exponent of the target binade
+    shift = np.minimum(23 - M + (et - e), 40).astype(np.uint64)
+    k = sig >> shift
+    rem = sig & ((np.uint64(1) << shift) - np.uint64(1))
+    half = np.uint64(1) << (shift - np.uint64(1))
+    up = (rem > half) | ((rem == half) & ((k & np.uint64(1)) == np.uint64(1)))
+    k = k + up.astype(np.uint64)
+    # normal: k in [2^M, 2^(M+1)] -> ((e - emin + 1) << M) + k - 2^M; subnormal: the code is k itself
+    code = ((et - emin).astype(np.uint64) << np.uint64(M)) + k
+    code = np.where(mag == 0, np.uint64(0), code) | sign
+    code = np.where(nan, np.uint64(0x80 | FP8_MAX_CODE[fmt]), code)
+    return code.astype(np.uint8)
+
+
+def _fp8_table(fmt):
+    M, emin = _FP8_MBITS[fmt], _FP8_EMIN[fmt]
+    t = np.empty(256, dtype=np.float64)
+    for c in range(256):
+        eb, m = (c & 0x7F) >> M, c & ((1 << M) - 1)
+        if fmt == 0 and (c & 0x7F) == 0x7F:
+            v = math.nan
+        elif fmt == 1 and eb == 31:
+            v = math.inf if m == 0 else math.nan
+        elif eb == 0:
+            v = m * 2.0 ** (emin - M)
+        else:
+            v = (1 + m / 2.0 ** M) * 2.0 ** (eb - 1 + emin)
+        t[c] = -v if c & 0x80 else v
+    return t
+
+
+_FP8_TABLE = (_fp8_table(0), _fp8_table(1))
+
+
+def fp8_decode(codes, fmt):
+    """uint8 codes -> float64 values (NaN / inf codes included), from the format's formula."""
+    if torch.is_tensor(codes):
+        codes = codes.detach().cpu().numpy()
+    return _FP8_TABLE[fmt][np.asarray(codes, dtype=np.uint8)]
+
+
+def fp8_finite_codes(fmt):
+    """Every code with a finite value, both signs (254 for e4m3fn, 248 for e5m2)."""
+    return np.array([c for c in range(256) if (c & 0x7F) <= FP8_MAX_CODE[fmt]], dtype=np.uint8)
+
+
+def fp8_midpoints(fmt):
+    """float64 midpoints between adjacent non-negative values, from 0 | smallest subnormal up to
+    the one below FMAX, and the codes on either side. All are exact in float32."""
+    lo = np.arange(0, FP8_MAX_CODE[fmt], dtype=np.uint8)
+    return (fp8_decode(lo, fmt) + fp8_decode(lo + 1, fmt)) / 2, lo, lo + 1
+
+
+def fp8_scale(amax32, fmt):
+    """scale_from: float32(FMAX) / amax if amax > 0 else 1, one float32 divide."""
+    a = np.float32(amax32)
+    with np.errstate(all="ignore"):
+        return np.float32(FP8_FMAX[fmt]) / a if a > 0 else np.float32(1)
+
+
+def fp8_dq(s32):
+    with np.errstate(all="ignore"):
+        return np.float32(1) / np.float32(s32)
+
+
+def fp8_cast_ref(x, s32, fmt):
+    """codes of float32(x) * float32(s), the multiply in float32."""
+    with np.errstate(all="ignore"):
+        return fp8_encode(_np32(x) * np.float32(s32), fmt)
+
+
+def fp8_amax(x):
+    """max |x| as the kernels form it: fmaxf from 0, which drops NaN."""
+    a = np.abs(_np32(x)).reshape(-1)
+    a = a[~np.isnan(a)]
+    return np.float32(a.max()) if a.size else np.float32(0)
+
+
+def fp8_amax_partials(x, nblk):
+    """pdt_amax_partial's index map: block b reduces elements [2048 (b + k nblk), + 2048), k = 0, 1, ..."""
+    a = np.abs(_np32(x)).reshape(-1)
+    a = np.where(np.isnan(a), np.float32(0), a)
+    chunks = -(-a.size // 2048)
+    rounds = -(-chunks // nblk)
+    pad = np.zeros(rounds * nblk * 2048, dtype=np.float32)
+    pad[:a.size] = a
+    return pad.reshape(rounds, nblk, 2048).max(axis=(0, 2))
+
+
+def _f32_bits(v):
+    return int(np.array(v, dtype=np.float32).view(np.uint32))
+
+
+class fp8_meta_ref:
+    """The 21-word delayed-scaling state of csrc/fp8.hip in plain Python: [0] scale in use, [1] dq
+    of the last cast, [2] amax of the running cast (bits), [3] unused, [4] history index (integer),
+    [5 .. 21) amax history. seed / roll / roll_partial are the three kernels that write it."""
+
+    def __init__(self, fmt, words=None):
+        self.fmt = fmt
+        self.scale, self.dq, self.amax, self.unused, self.idx = np.float32(0), np.float32(0), np.float32(0), 0, 0
+        self.hist = [np.float32(0)] * FP8_HIST
+        if words is not None:
+            w = np.asarray(words, dtype=np.uint32)
+            f = w.view(np.float32)
+            self.scale, self.dq, self.amax = f[0], f[1], f[2]
+            self.unused, self.idx = int(w[3]), int(w[4])
+            self.hist = [f[5 + i] for i in range(FP8_HIST)]
+
+    def seed(self, amax32):
+        self.hist = [np.float32(0)] * FP8_HIST
+        self.hist[0] = np.float32(amax32)
+        self.idx, self.amax, self.unused = 1, np.float32(0), 0
+        self.scale = fp8_scale(amax32, self.fmt)
+        self.dq = fp8_dq(self.scale)
+
+    def roll(self, amax32):
+        """One delayed cast of a tensor with this amax: returns (scale it was cast with, dq_out)."""
+        used, dq = self.scale, fp8_dq(self.scale)
+        cur = np.float32(max(np.float32(amax32), self.amax))  # atomicMax onto the slot's content
+        self.hist[self.idx % FP8_HIST] = cur
+        self.idx += 1
+        h = np.float32(0)
+        for v in self.hist:
+            h = v if v > h else h  # fmaxf from 0
+        self.dq = dq
+        self.scale = fp8_scale(h, self.fmt)
+        self.amax = np.float32(0)
+        return used, dq
+
+    def roll_partial(self, partials):
+        """pdt_fp8_meta_roll_partial: the amax is the largest partial or the slot, whichever is larger."""
+        return self.roll(fp8_amax(partials))
+
+    def words(self):
+        """The state as 21 uint32 words, for a bitwise comparison with the device's."""
+        w = [_f32_bits(self.scale), _f32_bits(self.dq), _f32_bits(self.amax), self.unused, self.idx & 0xFFFFFFFF]
+        return np.array(w + [_f32_bits(v) for v in self.hist], dtype=np.uint32)
+
+
+def meta_words(meta):
+    """A device meta tensor (21 fp32 words) as uint32 numpy words."""
+    return meta.detach().cpu().contiguous().view(torch.int32).numpy().view(np.uint32).copy()
+
+
+def assert_same_bits(out, ref, what=""):
+    """Bitwise equality of two arrays / tensors of the same item size (codes, float32 words):
+    zero mismatches, and NaNs compare by pattern."""
+    def raw(t):
+        if torch.is_tensor(t):
+            t = t.detach().cpu().contiguous()
+            t = t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()]).numpy()
+        t = np.ascontiguousarray(t)
+        return t.view({1: np.uint8, 2: np.uint16, 4: np.uint32}[t.itemsize])
+    o, r = raw(out), raw(ref)
+    assert o.shape == r.shape, (what, o.shape, r.shape)
+    bad = o != r
+    if bad.any():
+        i = int(np.flatnonzero(bad.reshape(-1))[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.size} words differ; first at flat index {i}: "
+                             f"out=0x{int(o.reshape(-1)[i]):x} ref=0x{int(r.reshape(-1)[i]):x}")
+
+
+def fp8_exhaustive_inputs(fmt, s32):
+    """(bf16 bit patterns int16 tensor, float32 array) for the exhaustive rounding test at scale s:
+    every bf16 pattern that is not a NaN (+-inf and both zeros kept); and the same values as float32
+    followed by, for every code midpoint m (and FMAX plus half a step) and both signs, float32(m / s)
+    and its two float32 neighbours. At a power-of-two s these are exact ties and one ulp either side."""
+    pat = np.arange(65536, dtype=np.uint32)
+    pat = pat[~(((pat & 0x7F80) == 0x7F80) & ((pat & 0x7F) != 0))]
+    as32 = (pat << 16).astype(np.uint32).view(np.float32)
+    mids, _, _ = fp8_midpoints(fmt)
+    top = FP8_FMAX[fmt] + (FP8_FMAX[fmt] - fp8_decode(np.uint8(FP8_MAX_CODE[fmt] - 1), fmt)) / 2
+    m = (np.append(mids, top) / np.float64(np.float32(s32))).astype(np.float32)
+    near = np.concatenate([np.nextafter(m, np.float32(0)), m, np.nextafter(m, np.float32(np.inf))])
+    x32 = np.concatenate([as32, near, -near]).astype(np.float32)
+    return torch.from_numpy(pat.astype(np.uint16).view(np.int16).copy()), x32
+
+
+def fp8_boundary_check(codes, prod64, absx64, s32, allow, fmt, what=""):
+    """The condition on codes of a product x * f(z) whose fp32 factor f is only known to within
+    ``allow`` of the float64 one: a code may differ from fp8_cast_ref(float32(prod64), s) only by
+    one step, and only where prod64 * s lies within allow * |x| * s of a rounding boundary (a
+    midpoint between adjacent values, or 0 between the two zeros). Returns the number of codes that differ."""
+    if torch.is_tensor(codes):
+        codes = codes.detach().cpu().numpy()
+    codes = np.asarray(codes, dtype=np.uint8).reshape(-1)
+    p = np.asarray(prod64, dtype=np.float64).reshape(-1)
+    ax = np.asarray(absx64, dtype=np.float64).reshape(-1)
+    s = np.float64(np.float32(s32))
+    ref = fp8_cast_ref(p.astype(np.float32), s32, fmt).reshape(-1)
+    diff = codes != ref
+    if diff.any():
+        # (0 is a boundary too: it separates the codes of -0 and +0, which count as adjacent)
+        mids = np.sort(np.concatenate([fp8_midpoints(fmt)[0], [0.0], -fp8_midpoints(fmt)[0]]))
+        t = p * s
+        j = np.clip(np.searchsorted(mids, t), 1, mids.size - 1)
+        dist = np.minimum(np.abs(t - mids[j - 1]), np.abs(t - mids[j]))
+        near = dist <= allow * ax * s
+
+        def order(c):  # signed position of a code among the values
+            c = c.astype(np.int64)
+            return np.where(c & 0x80, -(c & 0x7F), c & 0x7F)
+        step = np.abs(order(codes) - order(ref)) <= 1
+        bad = diff & ~(near & step)
+        if bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            raise AssertionError(f"{what}: {int(bad.sum())} codes differ away from a rounding boundary or by more "
+                                 f"than a step; first at {i}: out=0x{codes[i]:02x} ref=0x{ref[i]:02x} "
+                                 f"product*s={t[i]!r} distance={dist[i]!r} allowed={allow * ax[i] * s!r}")
+    return int(diff.sum())
+
+
+FP8_PLANT = 17.25
+
+
+def fp8_cast_inputs(n, bf16, seed, fmt=0):
+    """float32 array for the current-scaling cast tests: normal data of std 3 with |x| < 16 (so a
+    planted +-17.25 is the amax), bf16-representable when ``bf16``. A product of a bf16 value by
+    FMAX / 17.25 never comes within an fp32 ulp of a tie, so on bf16 data x / dq and x * s give the
+    same codes; the fp32 data of n >= 2047 therefore carries, from index 64 on and with alternating
+    signs, float32(m / s) and its two neighbours for every code midpoint m below 15.5 s."""
+    x = (torch.randn(n, generator=gen(seed, torch.device("cpu"))) * 3).clamp(-15.5, 15.5)
+    if bf16:
+        return x.to(torch.bfloat16).float().numpy()
+    x = x.numpy()
+    if n >= 2047:
+        s = fp8_scale(FP8_PLANT, fmt)
+        m = (fp8_midpoints(fmt)[0] / np.float64(s)).astype(np.float32)
+        m = m[m < 15.5]
+        near = np.stack([np.nextafter(m, np.float32(0)), m, np.nextafter(m, np.float32(np.inf))], 1).reshape(-1)
+        near[1::2] *= -1
+        assert 64 + near.size <= 2040
+        x[64:64 + near.size] = near
+    return x
+
+
+def fp8_script():
+    """(amax of the seeding tensor, amaxes of the 40 delayed casts that follow): every value is a
+    bf16 number. The seed (4) is larger than every ordinary step (<= 3), step 2 is a spike (64) and
+    step 9 an all-zero tensor: the scale must forget the seed 16 rolls after it and the spike
+    exactly 16 steps after it entered."""
+    steps = [0.75 + 0.25 * ((3 * k) % 10) for k in range(40)]
+    steps[2], steps[9] = 64.0, 0.0
+    return 4.0, steps
+
+
+def fp8_boundary_scale(allow, xmax, fmt):
+    """The scale for fp8_boundary_check's cases: the condition allows one step, so the uncertainty
+    allow * |x| * s must stay below half the smallest step of the format (2^-10 for e4m3, 2^-17 for
+    e5m2). The largest power of two that keeps it there, times 7/8 so that it is no power of two,
+    and at most FMAX / 5."""
+    half_step = 2.0 ** (_FP8_EMIN[fmt] - _FP8_MBITS[fmt] - 1)
+    p = 2.0 ** math.floor(math.log2(half_step / (allow * xmax)))
+    return np.float32(min(p * 0.875, FP8_FMAX[fmt] / 5))

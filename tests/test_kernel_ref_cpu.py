@@ -3,8 +3,11 @@
 * every float64 reference against PyTorch's own float64 CPU op at 1e-12 relative;
 * every metric rejects a seeded fault and accepts a faithful fp32 emulation of the kernel
   (torch fp32 on the CPU, output cast to bf16);
-* every exact-family input really is exact: its fp32 emulation equals the float64 reference.
+* every exact-family input really is exact: its fp32 emulation equals the float64 reference;
+* the fp8 mirror (fp8_encode / fp8_decode / fp8_meta_ref) against PyTorch's CPU float8 cast on every
+  bf16 pattern, and the inputs of tests/test_fp8_cast_kernels_gpu.py against seeded faults.
 """
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -419,3 +422,245 @@ def test_bf16_close_accepts_emulations_of_each_family():
     dy = kr.normal(tuple(yv.shape), gg)
     dx, ab = kr.maxpool_bwd_ref(dy, idx, 8, 9, 3, 1, 1)
     kr.assert_bf16_close(dx.to(torch.float32).to(BF), dx, ab, "pool bwd")
+
+
+# ----------------------------------------------------------------------- fp8 quantization
+FP8_DT = (torch.float8_e4m3fn, torch.float8_e5m2)
+FMTS = [0, 1]
+
+
+def torch_codes(x32, fmt):
+    """PyTorch's CPU cast of the clamped values (the library cast fp8_encode is independent of)."""
+    t = torch.from_numpy(np.ascontiguousarray(x32, dtype=np.float32))
+    return t.clamp(-kr.FP8_FMAX[fmt], kr.FP8_FMAX[fmt]).to(FP8_DT[fmt]).view(torch.uint8).numpy()
+
+
+def faulty_encode(v32, fmt, fault):
+    """fp8_encode with one seeded fault, by search in the table of values (float64):
+    'trunc' rounds toward zero, 'away' rounds ties away from zero, 'noclamp' lets values past FMAX
+    overflow (NaN code of e4m3fn, infinity code of e5m2), 'fmax240' clamps at 240."""
+    v = np.asarray(v32, dtype=np.float32).astype(np.float64)
+    vals = kr.fp8_decode(np.arange(kr.FP8_MAX_CODE[fmt] + 1, dtype=np.uint8), fmt)
+    fmax = 240.0 if fault == "fmax240" else kr.FP8_FMAX[fmt]
+    a = np.abs(v)
+    over = a > fmax + (vals[-1] - vals[-2]) / 2 if fault == "noclamp" else np.zeros(a.shape, dtype=bool)
+    a = np.minimum(a, fmax)
+    lo = np.clip(np.searchsorted(vals, a, side="right") - 1, 0, vals.size - 1)
+    hi = np.minimum(lo + 1, vals.size - 1)
+    mid = (vals[lo] + vals[hi]) / 2
+    if fault == "trunc":
+        up = np.zeros(a.shape, dtype=bool)
+    elif fault == "away":
+        up = a >= mid
+    else:
+        up = (a > mid) | ((a == mid) & (lo % 2 == 1))
+    code = np.where(up & (hi > lo), hi, lo)
+    code = np.where(over, 0x7F if fmt == 0 else 0x7C, code)
+    return (code | np.where(np.signbit(v), 0x80, 0)).astype(np.uint8)
+
+
+@pytest.mark.parametrize("fmt", FMTS)
+def test_fp8_decode_encode_identity_and_table(fmt):
+    codes = kr.fp8_finite_codes(fmt)
+    assert codes.size == (254 if fmt == 0 else 248)
+    vals = kr.fp8_decode(codes, fmt)
+    assert np.isfinite(vals).all() and np.abs(vals).max() == kr.FP8_FMAX[fmt]
+    assert kr.fp8_decode(np.uint8(kr.FP8_MAX_CODE[fmt]), fmt) == kr.FP8_FMAX[fmt]
+    kr.assert_same_bits(kr.fp8_encode(vals.astype(np.float32), fmt), codes, "decode . encode")
+    assert kr.fp8_encode(np.float32([0.0, -0.0]), fmt).tolist() == [0x00, 0x80]
+    # the formula's table against the library's, all 256 codes (NaN codes as NaN)
+    lib = torch.arange(256, dtype=torch.uint8).view(FP8_DT[fmt]).double().numpy()
+    mine = kr.fp8_decode(np.arange(256, dtype=np.uint8), fmt)
+    assert ((lib == mine) | (np.isnan(lib) & np.isnan(mine))).all()
+
+
+@pytest.mark.parametrize("fmt", FMTS)
+def test_fp8_encode_midpoints_go_to_even(fmt):
+    mids, lo, hi = kr.fp8_midpoints(fmt)
+    m32 = mids.astype(np.float32)
+    assert (m32.astype(np.float64) == mids).all() and mids[0] == kr.fp8_decode(np.uint8(1), fmt) / 2
+    even = np.where(lo % 2 == 0, lo, hi)
+    below, above = np.nextafter(m32, np.float32(0)), np.nextafter(m32, np.float32(np.inf))
+    for sgn, bit in ((1, 0), (-1, 0x80)):
+        kr.assert_same_bits(kr.fp8_encode(sgn * m32, fmt), even | bit, "tie")
+        kr.assert_same_bits(kr.fp8_encode(sgn * below, fmt), lo | bit, "one ulp below a tie")
+        kr.assert_same_bits(kr.fp8_encode(sgn * above, fmt), hi | bit, "one ulp above a tie")
+
+
+@pytest.mark.parametrize("fmt", FMTS)
+def test_fp8_encode_saturates(fmt):
+    fmax = np.float32(kr.FP8_FMAX[fmt])
+    big = np.float32([np.nextafter(fmax, np.float32(np.inf)), fmax * 1.07, fmax * 2, 3e38, np.inf])
+    assert (kr.fp8_encode(big, fmt) == kr.FP8_MAX_CODE[fmt]).all()
+    assert (kr.fp8_encode(-big, fmt) == (0x80 | kr.FP8_MAX_CODE[fmt])).all()
+    # the clamp as the kernel writes it, fminf(fmaxf(NaN, -FMAX), FMAX), gives -FMAX
+    assert (kr.fp8_encode(np.float32([np.nan, -np.nan]), fmt) == (0x80 | kr.FP8_MAX_CODE[fmt])).all()
+
+
+@pytest.mark.parametrize("fmt", FMTS)
+def test_fp8_encode_matches_torch_cpu_cast(fmt):
+    pat, _ = kr.fp8_exhaustive_inputs(fmt, 1.0)
+    assert pat.numel() == 65536 - 2 * 127
+    xb = pat.view(BF).float().numpy()
+    kr.assert_same_bits(kr.fp8_encode(xb, fmt), torch_codes(xb, fmt), "all bf16 patterns")
+    gg = g(40 + fmt)
+    x = torch.randn(400000, generator=gg) * torch.exp2(torch.rand(400000, generator=gg) * 37 - 20)
+    assert x.abs().min() < 2.0 ** -19 and x.abs().max() > 2.0 ** 16
+    kr.assert_same_bits(kr.fp8_encode(x, fmt), torch_codes(x.numpy(), fmt), "random fp32")
+    for s in (2.0 ** -3, 448.0 / 17, 57344.0 / 3):
+        _, x32 = kr.fp8_exhaustive_inputs(fmt, s)
+        with np.errstate(all="ignore"):
+            v = x32 * np.float32(s)
+        kr.assert_same_bits(kr.fp8_cast_ref(x32, s, fmt), torch_codes(v, fmt), f"exhaustive set at s={s}")
+
+
+def test_fp8_scale_and_meta_ref():
+    assert kr.fp8_scale(0.0, 0) == 1 and kr.fp8_scale(np.inf, 1) == 0 and kr.fp8_dq(np.float32(0)) == np.inf
+    assert kr.fp8_scale(17.0, 0) == np.float32(448) / np.float32(17)
+    m = kr.fp8_meta_ref(1)
+    m.seed(4.0)
+    assert m.idx == 1 and m.scale == np.float32(14336) and m.dq == np.float32(1 / 14336) and m.hist[0] == 4
+    used, dq = m.roll(64.0)
+    assert used == np.float32(14336) and dq == m.dq and m.hist[1] == 64 and m.scale == np.float32(896) and m.idx == 2
+    w = m.words()
+    assert w.dtype == np.uint32 and w.size == kr.FP8_META_WORDS and w[4] == 2 and w[2] == 0
+    kr.assert_same_bits(kr.fp8_meta_ref(1, w).words(), w, "round trip")
+    m.amax = np.float32(100)  # a preset slot above the cast's amax wins
+    m.roll_partial(np.float32([1, 3, 2]))
+    assert m.hist[2] == 100 and m.amax == 0
+    # the partial index map: block b of nblk takes 2048-element chunks b, b + nblk, ...
+    x = np.zeros(3 * 2048 + 5, dtype=np.float32)
+    x[0], x[2048], x[2 * 2048 + 7], x[-1] = -1, 2, -3, 4
+    assert kr.fp8_amax_partials(x, 4).tolist() == [1, 2, 3, 4]
+    assert kr.fp8_amax_partials(x, 2).tolist() == [3, 4] and kr.fp8_amax(x) == 4
+
+
+@pytest.mark.parametrize("fmt", FMTS)
+@pytest.mark.parametrize("fault", ["trunc", "away", "noclamp", "fmax240"])
+def test_fp8_exhaustive_set_rejects_rounding_and_clamp_faults(fmt, fault):
+    """The inputs of the GPU rounding test, at each of its scales, under code equality."""
+    for s in (1.0, 2.0 ** -3, 2.0 ** 5, 448.0 / 17, 57344.0 / 3):
+        pat, x32 = kr.fp8_exhaustive_inputs(fmt, s)
+        for x in (pat.view(BF).float().numpy(), x32):
+            with np.errstate(all="ignore"):
+                v = x * np.float32(s)
+            ref = kr.fp8_cast_ref(x, s, fmt)
+            fin = ~np.isnan(v)
+            kr.assert_same_bits(faulty_encode(v[fin], fmt, "none"), ref[fin], "the emulation without a fault")
+            if fault == "fmax240" and fmt == 1:
+                continue  # (240 is an e4m3 maximum; e5m2 has no such neighbour format)
+            if fault == "away" and s not in (1.0, 2.0 ** -3, 2.0 ** 5):
+                continue  # (a product by 448/17 or 57344/3 need not land on a tie: the power-of-two scales hold them)
+            with pytest.raises(AssertionError):
+                kr.assert_same_bits(faulty_encode(v[fin], fmt, fault), ref[fin], fault)
+    if fault == "away":  # ties are the only difference, and the bf16 patterns at s = 1 hold them
+        x = kr.fp8_exhaustive_inputs(fmt, 1.0)[0].view(BF).float().numpy()
+        bad = faulty_encode(x, fmt, fault) != kr.fp8_cast_ref(x, 1.0, fmt)
+        mids = kr.fp8_midpoints(fmt)[0]
+        assert bad.any() and np.isin(np.abs(x[bad]).astype(np.float64), mids).all()
+
+
+@pytest.mark.parametrize("fmt", FMTS)
+def test_fp8_cast_inputs_reject_divide_by_dq(fmt):
+    """x / dq is not x * s: the fp32 inputs of the current-scaling cast test hold values whose
+    product lies an ulp from a tie, where the two differ (in few codes: a ratio test passes it)."""
+    x = kr.fp8_cast_inputs(2049, 0, 7, fmt).copy()
+    x[-1] = -kr.FP8_PLANT
+    s = kr.fp8_scale(kr.fp8_amax(x), fmt)
+    assert s == np.float32(kr.FP8_FMAX[fmt]) / np.float32(kr.FP8_PLANT)
+    ref = kr.fp8_cast_ref(x, s, fmt)
+    div = kr.fp8_encode(x / kr.fp8_dq(s), fmt)
+    same = (div == ref).mean()
+    assert 0.9 < same < 1.0, same
+    with pytest.raises(AssertionError):
+        kr.assert_same_bits(div, ref, "x / dq")
+    _, x32 = kr.fp8_exhaustive_inputs(fmt, 57344.0 / 3)  # ... and so do those of the rounding test
+    s = np.float32(57344.0 / 3)
+    with np.errstate(all="ignore"):
+        assert (kr.fp8_encode(x32 / kr.fp8_dq(s), fmt) != kr.fp8_cast_ref(x32, s, fmt)).any()
+
+
+def test_fp8_code_equality_rejects_stale_tail_and_shifted_group():
+    x = kr.fp8_cast_inputs(2049, 1, 8)
+    ref = kr.fp8_cast_ref(x, 448.0 / 17, 0)
+    out = kr.guarded(2049, torch.uint8, CPU)
+    out.copy_(torch.from_numpy(ref))
+    kr.assert_same_bits(out, ref, "all written")
+    out[-1] = kr.POISON_BYTE  # the scalar tail's one byte left as it was
+    assert ref[-1] != kr.POISON_BYTE
+    with pytest.raises(AssertionError):
+        kr.assert_same_bits(out, ref, "stale tail byte")
+    kr.check_guards()
+    R, C = 65, 63
+    w = kr.fp8_cast_inputs(R * C, 0, 9).reshape(R, C)
+    q = kr.fp8_cast_ref(w, 448.0 / 16, 0)
+    qt = np.ascontiguousarray(q.T)
+    kr.assert_same_bits(torch.from_numpy(qt.copy()), q.T, "transpose")
+    bad = qt.copy()
+    bad[62, 60:64] = qt[62, 61:65]  # the last column's last whole 4-row group, one row late
+    assert (bad != qt).any()
+    with pytest.raises(AssertionError):
+        kr.assert_same_bits(bad, q.T, "shifted 4-row group")
+
+
+class _sticky_slot0(kr.fp8_meta_ref):
+    """The seeded history fault: the ring wraps over slots 1 .. 15 and never overwrites slot 0."""
+
+    def roll(self, amax32):
+        real, self.idx = self.idx, (self.idx if self.idx < kr.FP8_HIST else 1 + (self.idx - 1) % (kr.FP8_HIST - 1))
+        out = super().roll(amax32)
+        self.idx = real + 1
+        return out
+
+
+@pytest.mark.parametrize("fmt", FMTS)
+def test_fp8_script_forgets_seed_and_spike(fmt):
+    seed, steps = kr.fp8_script()
+    assert len(steps) == 40 and steps[2] == max(steps) and 0.0 in steps and seed > sorted(steps)[-2]
+    assert all(float(torch.tensor(a).to(BF)) == a for a in steps + [seed])
+    good, bad = kr.fp8_meta_ref(fmt), _sticky_slot0(fmt)
+    good.seed(seed)
+    bad.seed(seed)
+    fmax = np.float32(kr.FP8_FMAX[fmt])
+    first_diff = None
+    for k, a in enumerate(steps):
+        good.roll(a)
+        bad.roll(a)
+        if 2 <= k <= 17:
+            assert good.scale == fmax / np.float32(64), k  # the spike rules for exactly 16 steps
+        if k == 18:
+            assert good.scale == fmax / np.float32(max(steps[3:19])), k
+        if first_diff is None and (good.words() != bad.words()).any():
+            first_diff = k
+    assert good.idx == 41  # two wraps of the 16-slot ring
+    assert first_diff == 15, first_diff  # the roll that should overwrite slot 0 (the seed)
+    assert bad.scale == fmax / np.float32(seed) and good.scale > bad.scale  # ... and it never forgets it
+
+
+@pytest.mark.parametrize("fmt", FMTS)
+def test_fp8_boundary_condition_holds_for_an_fp32_gelu_grad(fmt):
+    """The GELU-gradient cast's condition (kr.fp8_boundary_check), on the CPU: codes of an fp32
+    x * gelu'(z) stay within it, with the allowance measured as the GPU test measures it; codes one
+    step off away from a boundary, or two steps off, do not."""
+    gg = g(50 + fmt)
+    z = kr.normal((129 * 1032,), gg, std=2.0)
+    x = kr.ints((129 * 1032,), gg)
+    d64 = kr.gelu_tanh_grad_ref(z)
+    zz = z.float().requires_grad_()
+    F.gelu(zz, approximate="tanh").sum().backward()
+    e_ref = (zz.grad.double() - d64).abs().max().item()
+    allow = 4 * max(e_ref, kr.U * d64.abs().max().item())
+    s = kr.fp8_boundary_scale(allow, 8, fmt)
+    codes = kr.fp8_cast_ref((x.float() * zz.grad).numpy(), s, fmt)
+    p64, ax = (kr.f64(x) * d64).numpy(), kr.f64(x).abs().numpy()
+    ndiff = kr.fp8_boundary_check(codes, p64, ax, s, allow, fmt, "fp32 gelu'")
+    print(f"MEASURED fp8 boundary check fmt={fmt}: allowance {allow:.3e}, {ndiff} of {codes.size} codes differ")
+    # (nearly all of them are -0 for +0 at z < -5, where gelu' is below the fp32 op's absolute error)
+    assert ndiff < codes.size * 1e-2
+    ref = kr.fp8_cast_ref(p64.astype(np.float32), s, fmt)
+    i = int(np.flatnonzero((ref & 0x7F > 8) & (ref & 0x7F < kr.FP8_MAX_CODE[fmt] - 2))[0])
+    for delta in (1, 2):
+        bad = ref.copy()
+        bad[i] += delta
+        with pytest.raises(AssertionError):
+            kr.fp8_boundary_check(bad, p64, ax, s, 0.0 if delta == 1 else 1.0, fmt, "seeded")

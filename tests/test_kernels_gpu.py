@@ -5,11 +5,14 @@ differ). Run on an MI355X: ``pytest -m gpu tests/test_kernels_gpu.py``.
 The element and row kernels (BatchNorm passes, pooling, LayerNorm, GELU backward, cross-entropy,
 column sums) are checked here only at a few shapes and with max-abs / Frobenius tolerances; their
 per-path tests against float64 references, with exact-family inputs, guard bands and derived
-bounds, are test_bn_act_kernels_gpu.py, test_pool_kernels_gpu.py and test_row_kernels_gpu.py."""
+bounds, are test_bn_act_kernels_gpu.py, test_pool_kernels_gpu.py and test_row_kernels_gpu.py.
+The fp8 casts (csrc/fp8.hip) are tested code for code in test_fp8_cast_kernels_gpu.py."""
 import pytest
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+import kernel_ref as kr
 
 pytestmark = pytest.mark.gpu
 
@@ -545,9 +548,9 @@ def test_fp8_quantize_matches_torch_cast(fmt):
     torch.cuda.synchronize()
     fmax = 448.0 if fmt == 0 else 57344.0
     assert abs(dq.item() - 17.0 / fmax) < 1e-6 * 17.0 / fmax + 1e-12
-    ref = (x.float() / dq).to(torch.float8_e4m3fn if fmt == 0 else torch.float8_e5m2)
-    same = (ref.view(torch.uint8) == q).float().mean().item()
-    assert same > 0.999, same
+    s = kr.fp8_scale(17.0, fmt)
+    kr.assert_same_bits(dq, [kr.fp8_dq(s)], "dq")
+    kr.assert_same_bits(q, kr.fp8_cast_ref(x, s, fmt).reshape(q.shape), "codes")  # x * s, every code
     assert nrmerr(_f8(q, fmt) * dq, x) < (0.03 if fmt == 0 else 0.06)
 
 
