@@ -869,13 +869,19 @@ PDT_API int pdt_attn_set_bwd_single(int on) {
   return 0;
 }
 
+// PDT_ATTN_TILED=1 (or pdt_attn_set_tiled(1)): the 64-row tiled kernels at every T, also where
+// the whole-sequence ones apply (T <= 256)
+static int g_attn_tiled = -1;
 static int attn_seq_disabled() {
-  static int v = -1;
-  if (v < 0) {
+  if (g_attn_tiled < 0) {
     const char* e = getenv("PDT_ATTN_TILED");
-    v = (e && e[0] == '1') ? 1 : 0;
+    g_attn_tiled = (e && e[0] == '1') ? 1 : 0;
   }
-  return v;
+  return g_attn_tiled;
+}
+PDT_API int pdt_attn_set_tiled(int on) {
+  g_attn_tiled = on ? 1 : 0;
+  return 0;
 }
 
 PDT_API int pdt_attn_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, float scale, hipStream_t st) {

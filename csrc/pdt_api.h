@@ -17,6 +17,7 @@
 
 // attention.hip
 PDT_API int pdt_attn_set_bwd_single(int on);
+PDT_API int pdt_attn_set_tiled(int on);
 PDT_API int pdt_attn_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, float scale, hipStream_t st);
 PDT_API int pdt_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                          void* dqkv, int B, int T, int H, float scale, hipStream_t st);

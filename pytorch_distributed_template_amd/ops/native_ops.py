@@ -92,7 +92,7 @@ class OpTimer:
     the per-op, per-shape breakdown of a training step (scripts/op_profile.py). Query
     entry points (plans, row counts, workspace sizes) pass through untimed."""
     _QUERY = ("_rows", "_variants", "_plan", "_plan2", "_workspace", "_size", "_blocks", "_kind", "_resolve_variant",
-              "_part", "_words", "_grad_row", "_set_bwd_single")
+              "_part", "_words", "_grad_row", "_set_bwd_single", "_set_tiled")
 
     def __init__(self, lib):
         self._lib = lib

@@ -1,11 +1,13 @@
 """Float64 references, error metrics, guard-banded buffers and input families for the element
 and row kernels (csrc/bn_act.hip, pool.hip, layernorm.hip, xent.hip), and a bit-exact numpy float32
-mirror of the fp8 casts and their scaling state (csrc/fp8.hip; last section).
+mirror of the fp8 casts and their scaling state (csrc/fp8.hip), and float64 references, derived
+bounds and input families for the bf16 attention kernels (csrc/attention.hip, attention_cls.hip,
+the bf16 forward of attention_f8.hip; last section).
 
 Used by tests/test_kernel_ref_cpu.py (which checks this module against PyTorch's float64 CPU ops
 and against seeded faults) and by the GPU tests test_bn_act_kernels_gpu.py,
-test_pool_kernels_gpu.py, test_row_kernels_gpu.py and test_fp8_cast_kernels_gpu.py. A plain
-module: no fixtures, no pytest settings.
+test_pool_kernels_gpu.py, test_row_kernels_gpu.py, test_fp8_cast_kernels_gpu.py and
+test_attention_kernels_gpu.py. A plain module: no fixtures, no pytest settings.
 
 Every reference is a formula on float64 tensors (the fp32 op is never called and upcast). Every
 reference that feeds a bounded comparison also returns ``abs_terms``: the sum of the absolute
@@ -29,6 +31,61 @@ Bounds (U = 2^-24, the unit roundoff of fp32)
   unit, so it is exact, the result does not depend on the summation order, and it must EQUAL the
   float64 reference. A dropped, doubled or misaddressed row or column changes the result by at
   least one unit and is caught at any size.
+
+Attention (csrc/attention.hip, the bf16 instantiation of attention_f8.hip, attention_cls.hip)
+---------------------------------------------------------------------------------------------
+Section "attention" below. The references are float64 formulas on the bf16 inputs; the backward
+reference is a function of the ``out`` and ``lse`` the kernel is GIVEN (the tests hand it the
+forward reference's own rounded ones), so it differs from the kernel by rounding only. Scores live
+in the log2 domain: c = fp32(scale) * fp32(log2 e), one fp32 product as the launchers form it, and
+lse = log2 sum_k 2^(c s_k). Per query q, with s_k = sum_d q_d k_d:
+
+* eps_s, the absolute error of a computed c*s_k - m: s_k is an fp32 MFMA accumulation of 64 exact
+  bf16 products (64 roundings), then the product with c, c's own rounding, the subtraction of the
+  maximum (or of lse) and one spare: (64 + 4) roundings on terms of size <= c * sum_d |q_d k_d|,
+  doubled as everywhere above: eps_s = 2 (64 + 4) U c max_k sum_d |q_d k_d|. (|c s_k - m| <=
+  2 c max_k sum_d |q_d k_d|, which the doubling also covers.)
+* eps_p, the relative error of one probability before it is packed: an absolute error e of the
+  exponent is a relative error ln2 * e of 2^x. Forward: eps_p = ln2 eps_s + 2^-22. Backward, where
+  the exponent is c s - lse with lse of any size: eps_p = ln2 (eps_s + U |lse|) + 2^-22. The
+  2^-22 is an ALLOWANCE of 2 ulp for the hardware exp2 (v_exp_f32 is specified to 1 ulp), not a
+  derived term; it is four orders of magnitude below the 2^-8 that follows. An error of the
+  maximum m itself cancels: the same computed m enters every term and the normaliser.
+* 2^-8: P (and dS) are rounded to bf16 before the second GEMM (pack_p), each by at most 2^-8 of
+  itself.
+* out = sum_k p_k v_k / l, A_out = sum_k p_k |v_k|: the output's own rounding 2^-8 |ref|; every
+  numerator term is off by 2^-8 (packing) + eps_p, the normaliser l (summed from the UNROUNDED
+  fp32 exponentials) by eps_p: (2^-8 + 2 eps_p) A_out; and 8 further fp32 roundings on terms of
+  A_out (the accumulation steps of one MFMA chain count once each per 32 keys and are <= 8 at
+  T <= 321 together with 1/l, the product with it and the rescales by alpha of the online
+  kernels), doubled: 2 * 8 * U * A_out.
+* lse = m + log2 l: the exponents are off by eps_s, which moves log2 sum 2^(x_k) by at most eps_s;
+  the exp2 allowance moves l by 2^-22, log2 l by 2^-22 / ln2 <= 2^-21; log2f, the final add and
+  m's own rounding: 4 U |ref|; the sum l: every lane adds at most half the keys of a tile in one
+  chain (16 of 64, 16 of 32, or 4 per 16-key subtile), then 2 cross-lane adds and, in the online
+  kernels, 3 roundings per tile (alpha, l * alpha, + ls); adding a zero is exact. That chain has
+  n <= ln2 (T - 1) inexact steps for every kernel and T, so l is off by n U and log2 l by
+  n U / ln2 <= (T - 1) U. Bound: eps_s + 2^-21 + 4 U |ref| + (T - 1) U.
+* dV = P^T dO: 2^-8 |ref| + sum_q (2^-8 + eps_p(q)) p_qk |dO_q| + 2 * 8 * U sum_q p_qk |dO_q|.
+* dS = p (dP - delta), dP = dO . v, delta = dO . out (64-term fp32 dot products: 2 * 64 U times
+  their absolute terms): E_dS = (2^-8 + eps_p) p (|dP| + |delta|) + p (128 U sum_d |dO_d v_d| +
+  128 U sum_d |dO_d out_d|), the first term being the packing of dS and the error of p.
+  dQ = scale dS K, dK = scale dS^T Q: 2^-8 |ref| + scale sum E_dS |K or Q| + 2 * 8 * U scale
+  sum |dS| |K or Q|.
+* delta of the tiled path is an fp32 output: ``assert_f32_close`` with roundings = 64.
+* The class-token kernel works in fp32 throughout, natural-log domain, scale 1/8 (exact): no
+  packing term, no ln2 factor (eps_p = eps_s [+ U |lse|] + 2^-22 with c = 1/8; its dot products
+  are 8 FMAs and 3 lane adds, fewer than the 64 + 4 allowed), and the sums over keys (o, dq) are
+  chains of CLS_CHAIN = 16 roundings: <= 8 FMAs per thread (256 keys over 32 token groups), 3
+  lane adds, 3 adds over the waves, 1/l and the product with it.
+* Results below 2^-126 (fp32) or 2^-133 (bf16) flush to zero; every bound above is relative to a
+  sum that holds a probability >= 1/T, so this needs no term.
+
+Exact attention families: ``onehot`` (every query selects one key by a margin of >= 150 in c*s, so
+every other fp32 probability is exactly 0 and P, l are exactly 1: out, dV are rows of V, dO and
+dQ = dK = 0, all exactly) and ``counting`` (Q = 0: every key weighs exactly 1 before
+normalisation, so a dropped or doubled (q, k) pair moves an output by >= 1 / ceil(T / 64) of
+itself, against a bound of about 2^-8).
 """
 import math
 
@@ -713,3 +770,290 @@ def fp8_boundary_scale(allow, xmax, fmt):
     half_step = 2.0 ** (_FP8_EMIN[fmt] - _FP8_MBITS[fmt] - 1)
     p = 2.0 ** math.floor(math.log2(half_step / (allow * xmax)))
     return np.float32(min(p * 0.875, FP8_FMAX[fmt] / 5))
+
+
+# --------------------------------------------------------------------------------- attention
+# csrc/attention.hip, the bf16 instantiation of csrc/attention_f8.hip (pdt_attn_fwd_tiles) and
+# csrc/attention_cls.hip. qkv is [B][T][3][H][64], out / dout [B][T][H*64], lse / delta [B*H][T].
+# Bounds: module docstring, "Attention".
+LN2 = math.log(2.0)
+SCORE_ROUNDINGS = 64 + 4     # eps_s
+EXP2_ALLOW = 2.0 ** -22      # 2 ulp for the hardware exp2 (an allowance)
+LSE_EXP2 = 2.0 ** -21        # >= EXP2_ALLOW / ln2
+ACC_ROUNDINGS = 8            # fp32 roundings of an accumulator after the second GEMM
+DOT_ROUNDINGS = 64           # dP, delta: 64-term fp32 dot products
+CLS_CHAIN = 16               # the class-token kernel's sums over keys
+ONEHOT_GAP = 150.0
+
+
+def attn_c(scale):
+    """scale * log2(e) as the launchers form it: one fp32 product of two fp32 numbers."""
+    return float(np.float32(scale) * np.float32(1.4426950408889634))
+
+
+def attn_heads(qkv, H):
+    """[B][T][3*H*64] -> float64 q, k, v, each [B][H][T][64]."""
+    B, T, _ = qkv.shape
+    q, k, v = f64(qkv).view(B, T, 3, H, 64).permute(2, 0, 3, 1, 4)
+    return q, k, v
+
+
+def attn_rows(x, H):
+    """[B][T][H*64] -> float64 [B][H][T][64]."""
+    B, T, _ = x.shape
+    return f64(x).view(B, T, H, 64).transpose(1, 2)
+
+
+def attn_flat(x):
+    """[B][H][T][64] -> [B][T][H*64]."""
+    B, H, T, _ = x.shape
+    return x.transpose(1, 2).reshape(B, T, H * 64)
+
+
+def _attn_pack3(dq, dk, dv):
+    """three [B][H][T][64] -> [B][T][3*H*64]."""
+    B, H, T, _ = dq.shape
+    return torch.stack([dq, dk, dv]).permute(1, 3, 0, 2, 4).reshape(B, T, 3 * H * 64)
+
+
+def _top_gap(cs):
+    """Smallest distance over all queries between the largest and the second largest of cs[..., :]."""
+    if cs.shape[-1] < 2:
+        return math.inf
+    top = cs.topk(2, dim=-1).values
+    return float((top[..., 0] - top[..., 1]).min())
+
+
+def attn_fwd_ref(qkv, H, scale):
+    """dict(out [B][T][H*64], lse [B*H][T] (log2 domain of the scaled scores), A_out = sum_k p_k |v_k|,
+    sabs [B*H][T] = max_k sum_d |q_d k_d|, eps_s, out_bound, lse_bound, gap = the smallest margin in
+    c*s between a query's best and second-best key)."""
+    q, k, v = attn_heads(qkv, H)
+    B, _, T, _ = q.shape
+    c = attn_c(scale)
+    cs = c * (q @ k.transpose(-1, -2))
+    m = cs.max(-1, keepdim=True).values
+    e = torch.exp2(cs - m)
+    l = e.sum(-1, keepdim=True)
+    P = e / l
+    lse = (m + torch.log2(l)).reshape(B * H, T)
+    out, A = attn_flat(P @ v), attn_flat(P @ v.abs())
+    sabs = (q.abs() @ k.abs().transpose(-1, -2)).max(-1, keepdim=True).values   # [B][H][T][1]
+    eps_s = 2 * SCORE_ROUNDINGS * U * c * sabs
+    eps_p = attn_flat((LN2 * eps_s + EXP2_ALLOW).expand(B, H, T, 64))
+    return dict(out=out, lse=lse, A_out=A, sabs=sabs.reshape(B * H, T), eps_s=eps_s.reshape(B * H, T), c=c,
+                gap=_top_gap(cs),
+                out_bound=BF16_HALF * out.abs() + (BF16_HALF + 2 * eps_p) * A + 2 * ACC_ROUNDINGS * U * A,
+                lse_bound=eps_s.reshape(B * H, T) + LSE_EXP2 + 4 * U * lse.abs() + (T - 1) * U)
+
+
+def attn_bwd_ref(qkv, out, dout, lse, H, scale):
+    """The backward as a function of what the kernel is given (``out`` bf16, ``lse`` fp32):
+    P = exp2(c S - lse), dP = dO V^T, delta = rowsum(dO o out), dS = P o (dP - delta),
+    dQ = scale dS K, dK = scale dS^T Q, dV = P^T dO -> dict(dqkv [B][T][3*H*64], dqkv_bound,
+    delta [B*H][T], delta_abs)."""
+    q, k, v = attn_heads(qkv, H)
+    B, _, T, _ = q.shape
+    o, do = attn_rows(out, H), attn_rows(dout, H)
+    L = f64(lse).view(B, H, T, 1)
+    c, sc = attn_c(scale), float(np.float32(scale))
+    kt, vt = k.transpose(-1, -2), v.transpose(-1, -2)
+    P = torch.exp2(c * (q @ kt) - L)
+    dP = do @ vt
+    delta = (do * o).sum(-1, keepdim=True)
+    dS = P * (dP - delta)
+    dQ, dK, dV = sc * (dS @ k), sc * (dS.transpose(-1, -2) @ q), P.transpose(-1, -2) @ do
+    eps_s = 2 * SCORE_ROUNDINGS * U * c * (q.abs() @ k.abs().transpose(-1, -2)).max(-1, keepdim=True).values
+    eps_p = LN2 * (eps_s + U * L.abs()) + EXP2_ALLOW                            # per query [B][H][T][1]
+    delta_abs = (do * o).abs().sum(-1, keepdim=True)
+    E = (BF16_HALF + eps_p) * P * (dP.abs() + delta.abs()) + \
+        P * (2 * DOT_ROUNDINGS * U * (do.abs() @ vt.abs()) + 2 * DOT_ROUNDINGS * U * delta_abs)
+    acc = 2 * ACC_ROUNDINGS * U
+    bV = BF16_HALF * dV.abs() + ((BF16_HALF + eps_p) * P).transpose(-1, -2) @ do.abs() + \
+        acc * (P.transpose(-1, -2) @ do.abs())
+    bQ = BF16_HALF * dQ.abs() + sc * (E @ k.abs()) + acc * sc * (dS.abs() @ k.abs())
+    bK = BF16_HALF * dK.abs() + sc * (E.transpose(-1, -2) @ q.abs()) + acc * sc * (dS.abs().transpose(-1, -2) @ q.abs())
+    return dict(dqkv=_attn_pack3(dQ, dK, dV), dqkv_bound=_attn_pack3(bQ, bK, bV),
+                delta=delta.reshape(B * H, T), delta_abs=delta_abs.reshape(B * H, T))
+
+
+def attn_cls_ref(qkv, H, dout=None, o=None, lse=None):
+    """Token 0's query against all keys (header of csrc/attention_cls.hip): natural-log domain,
+    scale 1/8, fp32 throughout. Forward: dict(out [B][H*64], lse [B*H], out_bound, lse_bound, gap).
+    With ``dout`` [B][H*64] and the ``o`` (bf16) and ``lse`` (fp32) the kernel is given, also
+    dqkv [B][T][3*H*64] and dqkv_bound (dq of every token but 0: exactly 0, bound 0)."""
+    q, k, v = attn_heads(qkv, H)
+    B, _, T, _ = q.shape
+    q0 = q[:, :, :1]
+    kt = k.transpose(-1, -2)
+    s = 0.125 * (q0 @ kt)                                                        # [B][H][1][T]
+    eps_s = 2 * SCORE_ROUNDINGS * U * 0.125 * (q0.abs() @ kt.abs()).max(-1, keepdim=True).values
+    m = s.max(-1, keepdim=True).values
+    e = torch.exp(s - m)
+    l = e.sum(-1, keepdim=True)
+    P = e / l
+    L = (m + torch.log(l)).reshape(B * H)
+    out, A = (P @ v).reshape(B, H * 64), (P @ v.abs()).reshape(B, H * 64)
+    eps_p = (eps_s + EXP2_ALLOW).expand(B, H, 1, 64).reshape(B, H * 64)
+    ref = dict(out=out, lse=L, gap=_top_gap(s) / LN2,
+               out_bound=BF16_HALF * out.abs() + 2 * eps_p * A + 2 * CLS_CHAIN * U * A,
+               lse_bound=eps_s.reshape(B * H) + LSE_EXP2 + 4 * U * L.abs() + (T - 1) * U)
+    if dout is None:
+        return ref
+    do, og = f64(dout).view(B, H, 1, 64), f64(o).view(B, H, 1, 64)
+    Lg = f64(lse).view(B, H, 1, 1)
+    P = torch.exp(s - Lg)
+    dP = do @ v.transpose(-1, -2)                                                # [B][H][1][T]
+    delta = (do * og).sum(-1, keepdim=True)
+    dS = P * (dP - delta)
+    eps_p = eps_s + U * Lg.abs() + EXP2_ALLOW
+    E = eps_p * P * (dP.abs() + delta.abs()) + \
+        P * (2 * DOT_ROUNDINGS * U * (do.abs() @ v.abs().transpose(-1, -2)) +
+             2 * DOT_ROUNDINGS * U * (do * og).abs().sum(-1, keepdim=True))
+    acc = 2 * ACC_ROUNDINGS * U
+    dQ, bQ = torch.zeros_like(q), torch.zeros_like(q)
+    dQ[:, :, :1] = 0.125 * (dS @ k)
+    bQ[:, :, :1] = BF16_HALF * dQ[:, :, :1].abs() + 0.125 * (E @ k.abs()) + 2 * CLS_CHAIN * U * 0.125 * (dS.abs() @ k.abs())
+    dSt, Et, Pt = dS.transpose(-1, -2), E.transpose(-1, -2), P.transpose(-1, -2)  # [B][H][T][1]
+    dK = 0.125 * dSt * q0
+    bK = BF16_HALF * dK.abs() + 0.125 * Et * q0.abs() + acc * 0.125 * dSt.abs() * q0.abs()
+    dV = Pt * do
+    bV = BF16_HALF * dV.abs() + (eps_p * P).transpose(-1, -2) * do.abs() + acc * Pt * do.abs()
+    ref.update(dqkv=_attn_pack3(dQ, dK, dV), dqkv_bound=_attn_pack3(bQ, bK, bV))
+    return ref
+
+
+ATTN_FAMILIES = ("onehot", "counting", "negative", "normal", "peaked")
+
+
+def attn_inputs(family, B, T, H, seed, device=None):
+    """dict(qkv bf16 [B][T][3*H*64], dout bf16 [B][T][H*64], sel) of one input family; every
+    (batch, head) gets different data.
+
+    onehot    K rows random +-8, Q[q] = 2 K[sel[q]] for a random permutation sel per (b, h) with
+              sel[0] = T - 1 and sel[T - 1] = 0 forced ("onehot0": sel[0] = 0, sel[T - 1] = T - 1),
+              V and dO integers in [-8, 8]. Raw selected score 64 * 128 = 8192; ``sel`` [B][H][T].
+    counting  Q = 0, K random integers, V[k] = 8 onehot((k + 5 bh) mod 64), dO[q] = 8 onehot((q + 11 bh)
+              mod 64) with bh = b H + h: out[q][d] = 8 n_d / T.
+    negative  K = |N(0,1)|, Q = -|N(0,1)|: every score far below the 0 of a padded (zero) key.
+    normal    N(0, 1.5^2), the regime of the older tests; dO N(0,1).
+    peaked    as normal with Q of std 4: probabilities span > 2^30 in a row, maxima anywhere."""
+    device = default_device() if device is None else device
+    g = gen(seed, device)
+    shape = (B, H, T, 64)
+    sel = None
+
+    def rnd(std):
+        return torch.randn(shape, generator=g, device=device) * std
+
+    if family in ("onehot", "onehot0"):
+        k = (torch.randint(0, 2, shape, generator=g, device=device) * 16 - 8).to(torch.float32)
+        sel = torch.empty((B, H, T), dtype=torch.long, device=device)
+        for i in range(B * H):
+            s = torch.arange(T, device=device)
+            if T > 2:
+                s[1:T - 1] = 1 + torch.randperm(T - 2, generator=g, device=device)
+            if family == "onehot" and T > 1:
+                s[0], s[T - 1] = T - 1, 0
+            sel[i // H, i % H] = s
+        q = 2 * torch.gather(k, 2, sel[..., None].expand(shape))
+        v, do = ints(shape, g, dtype=torch.float32), ints(shape, g, dtype=torch.float32)
+    elif family == "counting":
+        q, k = torch.zeros(shape, device=device), ints(shape, g, dtype=torch.float32)
+        bh = torch.arange(B * H, device=device).view(B, H, 1)
+        t = torch.arange(T, device=device).view(1, 1, T)
+        v = 8.0 * torch.nn.functional.one_hot((t + 5 * bh) % 64, 64)
+        do = 8.0 * torch.nn.functional.one_hot((t + 11 * bh) % 64, 64)
+    elif family == "negative":
+        q, k, v, do = -rnd(1.0).abs(), rnd(1.0).abs(), rnd(1.0), rnd(1.0)
+    elif family == "normal":
+        q, k, v, do = rnd(1.5), rnd(1.5), rnd(1.5), rnd(1.0)
+    elif family == "peaked":
+        q, k, v, do = rnd(4.0), rnd(1.5), rnd(1.5), rnd(1.0)
+    else:
+        raise ValueError(family)
+    return dict(family=family, qkv=_attn_pack3(q, k, v).to(torch.bfloat16).contiguous(),
+                dout=attn_flat(do.to(torch.float32)).to(torch.bfloat16).contiguous(), sel=sel)
+
+
+def attn_onehot_expect(inp, H):
+    """What the onehot family must give exactly: out[q] = V[sel[q]], and with that out and the
+    reference lse, dV[k] = dO[sel^-1[k]] and dQ = dK = 0 -> (out [B][T][H*64], dqkv [B][T][3*H*64])."""
+    _, _, v = attn_heads(inp["qkv"], H)
+    do = attn_rows(inp["dout"], H)
+    idx = inp["sel"][..., None].expand(v.shape)
+    out = torch.gather(v, 2, idx)
+    dv = torch.zeros_like(v).scatter_(2, idx, do)
+    return attn_flat(out), _attn_pack3(torch.zeros_like(v), torch.zeros_like(v), dv)
+
+
+def attn_check_fwd(inp, ref, out, lse, H, what=""):
+    """Every element of out and lse. onehot: out exactly, lse within 4 U |ref| (the gap condition is
+    asserted on the reference first); every other family: the derived bounds."""
+    if inp["family"] == "onehot":
+        assert ref["gap"] >= ONEHOT_GAP, (what, ref["gap"])
+        assert_exact(out, attn_onehot_expect(inp, H)[0], what + " out")
+        assert_close(lse, ref["lse"], 4 * U * ref["lse"].abs(), what + " lse")
+    else:
+        assert out.dtype == torch.bfloat16 and lse.dtype == torch.float32
+        assert_close(out, ref["out"], ref["out_bound"], what + " out")
+        assert_close(lse, ref["lse"], ref["lse_bound"], what + " lse")
+
+
+def attn_check_bwd(inp, bref, dqkv, H, what="", delta=None):
+    """Every element of d(qkv) (and of delta, where the path writes it) against ``attn_bwd_ref``
+    evaluated on the forward reference's rounded out and lse; onehot: exactly."""
+    if inp["family"] == "onehot":
+        assert_exact(dqkv, attn_onehot_expect(inp, H)[1], what + " dqkv")
+    else:
+        assert dqkv.dtype == torch.bfloat16
+        assert_close(dqkv, bref["dqkv"], bref["dqkv_bound"], what + " dqkv")
+    if delta is not None:
+        assert_f32_close(delta, bref["delta"], bref["delta_abs"], what + " delta", roundings=DOT_ROUNDINGS)
+
+
+# the sequence lengths of tests/test_attention_kernels_gpu.py (also walked on the CPU: the onehot gap)
+ATTN_B, ATTN_H, ATTN_SCALE = 2, 3, 0.125
+ATTN_T_FWD_SEQ = tuple(sorted({16 * n - d for n in range(1, 17) for d in (0, 15)} | {5, 197}))
+ATTN_T_TILES = tuple(sorted({32 * n - d for n in range(1, 9) for d in (0, 31)} | {197}))
+ATTN_T_TILED = (257, 320, 321)         # as dispatched
+ATTN_T_TILED_FORCED = (1, 63, 64, 65, 129)
+ATTN_T_BWD_SEQ = tuple(sorted({16 * n - d for n in (1, 2, 7, 8, 9, 13, 16) for d in (0, 15)} | {5}))
+ATTN_T_CLS = (1, 7, 31, 32, 33, 64, 197, 256)
+ATTN_T_ALL = tuple(sorted(set(ATTN_T_FWD_SEQ + ATTN_T_TILES + ATTN_T_TILED + ATTN_T_TILED_FORCED + ATTN_T_BWD_SEQ +
+                              ATTN_T_CLS)))
+
+
+def attn_seed(family, T):
+    return 1000 * (ATTN_FAMILIES + ("onehot0",)).index(family) + T
+
+
+def attn_cls_onehot_expect(inp, H):
+    """Class token, onehot families: out[b][h] = V[sel[b][h][0]], lse = 8192 / 8, dV of that key =
+    dO of token 0 and every other gradient 0 -> (out [B][H*64], dqkv [B][T][3*H*64])."""
+    _, _, v = attn_heads(inp["qkv"], H)
+    B, _, T, _ = v.shape
+    do = attn_rows(inp["dout"], H)[:, :, :1]
+    idx = inp["sel"][:, :, :1, None].expand(B, H, 1, 64)
+    dv = torch.zeros_like(v).scatter_(2, idx, do)
+    return torch.gather(v, 2, idx).reshape(B, H * 64), _attn_pack3(torch.zeros_like(v), torch.zeros_like(v), dv)
+
+
+def attn_check_cls_fwd(inp, ref, out, lse, H, what=""):
+    if inp["family"] in ("onehot", "onehot0"):
+        assert ref["gap"] >= ONEHOT_GAP, (what, ref["gap"])
+        assert_exact(out, attn_cls_onehot_expect(inp, H)[0], what + " out")
+        assert_close(lse, torch.full_like(ref["lse"], 1024.0), 4 * U * 1024.0, what + " lse")
+    else:
+        assert out.dtype == torch.bfloat16 and lse.dtype == torch.float32
+        assert_close(out, ref["out"], ref["out_bound"], what + " out")
+        assert_close(lse, ref["lse"], ref["lse_bound"], what + " lse")
+
+
+def attn_check_cls_bwd(inp, ref, dqkv, H, what=""):
+    """Every element of d(qkv): dq of every token but 0 has bound 0 (and NaN poison fails)."""
+    if inp["family"] in ("onehot", "onehot0"):
+        assert_exact(dqkv, attn_cls_onehot_expect(inp, H)[1], what + " dqkv")
+    else:
+        assert dqkv.dtype == torch.bfloat16
+        assert_close(dqkv, ref["dqkv"], ref["dqkv_bound"], what + " dqkv")

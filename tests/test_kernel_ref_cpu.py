@@ -5,8 +5,14 @@
   (torch fp32 on the CPU, output cast to bf16);
 * every exact-family input really is exact: its fp32 emulation equals the float64 reference;
 * the fp8 mirror (fp8_encode / fp8_decode / fp8_meta_ref) against PyTorch's CPU float8 cast on every
-  bf16 pattern, and the inputs of tests/test_fp8_cast_kernels_gpu.py against seeded faults.
+  bf16 pattern, and the inputs of tests/test_fp8_cast_kernels_gpu.py against seeded faults;
+* the attention references against float64 autograd, an fp32 emulation of the kernels' algorithm
+  (online softmax over key tiles, bf16-packed P and dS) inside every derived bound for every input
+  family, nine seeded faults each rejected by a named family, and the onehot family's margin at
+  every sequence length of tests/test_attention_kernels_gpu.py.
 """
+import math
+
 import numpy as np
 import pytest
 import torch
@@ -664,3 +670,249 @@ def test_fp8_boundary_condition_holds_for_an_fp32_gelu_grad(fmt):
         bad[i] += delta
         with pytest.raises(AssertionError):
             kr.fp8_boundary_check(bad, p64, ax, s, 0.0 if delta == 1 else 1.0, fmt, "seeded")
+
+
+# ------------------------------------------------------------------------------------ attention
+AB, AH, ASC = kr.ATTN_B, kr.ATTN_H, kr.ATTN_SCALE
+EMU_T = [5, 65, 197, 321]
+
+
+def _attn_case(family, T):
+    inp = kr.attn_inputs(family, AB, T, AH, kr.attn_seed(family, T), CPU)
+    fwd = kr.attn_fwd_ref(inp["qkv"], AH, ASC)
+    out_r, lse_r = fwd["out"].to(BF), fwd["lse"].to(torch.float32)
+    return inp, fwd, out_r, lse_r, kr.attn_bwd_ref(inp["qkv"], out_r, inp["dout"], lse_r, AH, ASC)
+
+
+_attn_cases = {}
+
+
+def attn_case(family, T):
+    if (family, T) not in _attn_cases:
+        _attn_cases[family, T] = _attn_case(family, T)
+    return _attn_cases[family, T]
+
+
+def test_attn_refs_match_torch_autograd():
+    """attn_fwd_ref / attn_bwd_ref / attn_cls_ref against float64 autograd attention. The backward
+    references take the unrounded O and the fp64 lse here, where their definition (delta from the
+    given out, P from the given lse) coincides with the derivative."""
+    B, T, H = 2, 37, 3
+    gg = g(60)
+    x = (torch.randn(B, T, 3 * H * 64, generator=gg, dtype=kr.F64) * 1.5).requires_grad_()
+    dout = torch.randn(B, T, H * 64, generator=gg, dtype=kr.F64)
+    q, k, v = x.view(B, T, 3, H, 64).permute(2, 0, 3, 1, 4)
+    s = (q @ k.transpose(-1, -2)) * 0.125
+    o = (torch.softmax(s, -1) @ v).transpose(1, 2).reshape(B, T, H * 64)
+    (o * dout).sum().backward()
+    f = kr.attn_fwd_ref(x, H, 0.125)
+    # (c is an fp32 product: it differs from 0.125 log2(e) by < 2^-24 relative, |c s| < 400 here)
+    assert rel(f["out"], o.detach()) < 1e-4
+    lse2 = torch.logsumexp(s.detach(), -1).reshape(B * H, T) / kr.LN2
+    assert rel(f["lse"], lse2) < 1e-7
+    assert bool((f["A_out"] >= f["out"].abs() - 1e-12).all()) and bool((f["out_bound"] > 0).all())
+    # with c exactly 0.125 log2(e) the formulas agree to 1e-12
+    c0 = kr.attn_c
+    try:
+        kr.attn_c = lambda scale: scale / kr.LN2
+        f = kr.attn_fwd_ref(x, H, 0.125)
+        assert rel(f["out"], o.detach()) < 1e-12 and rel(f["lse"], lse2) < 1e-12
+        b = kr.attn_bwd_ref(x, f["out"], dout, f["lse"], H, 0.125)
+        assert rel(b["dqkv"], x.grad) < 1e-12
+        assert rel(b["delta"], (dout * o.detach()).view(B, T, H, 64).sum(-1).permute(0, 2, 1).reshape(B * H, T)) < 1e-12
+        assert bool((b["dqkv_bound"] >= 0).all())
+    finally:
+        kr.attn_c = c0
+    # class token: the same attention, gradient flowing into token 0's output only
+    x2 = x.detach().clone().requires_grad_()
+    q, k, v = x2.view(B, T, 3, H, 64).permute(2, 0, 3, 1, 4)
+    s = (q[:, :, :1] @ k.transpose(-1, -2)) * 0.125
+    o0 = (torch.softmax(s, -1) @ v).reshape(B, H * 64)
+    (o0 * dout[:, 0]).sum().backward()
+    cf = kr.attn_cls_ref(x2, H)
+    assert rel(cf["out"], o0.detach()) < 1e-12
+    assert rel(cf["lse"], torch.logsumexp(s.detach(), -1).reshape(B * H)) < 1e-12
+    cb = kr.attn_cls_ref(x2, H, dout[:, 0], cf["out"], cf["lse"])
+    assert rel(cb["dqkv"], x2.grad) < 1e-12
+    dq = cb["dqkv"].view(B, T, 3, H * 64)[:, 1:, 0]
+    assert bool((dq == 0).all()) and bool((cb["dqkv_bound"].view(B, T, 3, H * 64)[:, 1:, 0] == 0).all())
+
+
+@pytest.mark.parametrize("T", kr.ATTN_T_ALL)
+def test_attn_onehot_gap_and_exactness(T):
+    """The onehot family at every T of the GPU file: every other key lies >= 150 below the selected
+    one in c*s (fp32 exp2 gives exactly 0), and the float64 references agree with the closed forms
+    V[sel], dO[sel^-1], 0 to far below an fp32 denormal."""
+    for fam in ("onehot", "onehot0"):
+        inp = kr.attn_inputs(fam, AB, T, AH, kr.attn_seed(fam, T), CPU)
+        sel = inp["sel"]
+        assert int(sel[0, 0, 0]) == (T - 1 if fam == "onehot" else 0) and int(sel[1, 2, T - 1]) == (0 if fam == "onehot" else T - 1)
+        assert bool((sel.sort(-1).values == torch.arange(T)).all())
+        f = kr.attn_fwd_ref(inp["qkv"], AH, ASC)
+        assert f["gap"] >= kr.ONEHOT_GAP, f["gap"]
+        assert kr.attn_cls_ref(inp["qkv"], AH)["gap"] >= kr.ONEHOT_GAP
+        out, dqkv = kr.attn_onehot_expect(inp, AH)
+        assert (f["out"] - out).abs().max().item() < 1e-100
+        assert bool((f["lse"] == f["c"] * 8192).all())
+        b = kr.attn_bwd_ref(inp["qkv"], f["out"].to(BF), inp["dout"], f["lse"].to(torch.float32), AH, ASC)
+        assert (b["dqkv"] - dqkv).abs().max().item() < 1e-100
+    if T > 1:
+        assert not torch.equal(sel[0, 0], sel[0, 1]) or T < 4
+
+
+def _heads32(x, H):
+    return [t.float() for t in kr.attn_heads(x, H)]
+
+
+def emulate_attn_fwd(inp, tile=64, fault=None):
+    """fp32 emulation of the kernels' algorithm: online softmax over ``tile`` keys with rescaling,
+    P packed to bf16 for the PV product, l summed from the unrounded exponentials, fp32
+    accumulation -> (out bf16 [B][T][H*64], lse fp32 [B*H][T]). ``fault``: one seeded fault."""
+    q, k, v = _heads32(inp["qkv"], AH)
+    B, H, T, _ = q.shape
+    c = torch.tensor(kr.attn_c(ASC), dtype=torch.float32)
+    Tp = -(-T // tile) * tile
+    k, v = F.pad(k, (0, 0, 0, Tp - T)), F.pad(v, (0, 0, 0, Tp - T))
+    if fault == "swap_v":
+        j = T // 2
+        v[:, :, [j, j + 1 if j + 1 < T else j - 1]] = v[:, :, [j + 1 if j + 1 < T else j - 1, j]]
+    m = torch.full((B, H, T, 1), -math.inf)
+    l, o = torch.zeros(B, H, T, 1), torch.zeros(B, H, T, 64)
+    for k0 in range(0, Tp, tile):
+        s = (q @ k[:, :, k0:k0 + tile].transpose(-1, -2)) * c
+        key = torch.arange(k0, k0 + tile)
+        valid = key < (T + 1 if fault == "unmasked" else T)
+        if fault == "skip_key":
+            valid = valid & (key != T // 2)
+        s = torch.where(valid, s, torch.tensor(-math.inf))
+        mn = torch.maximum(m, s.max(-1, keepdim=True).values)
+        alpha = torch.exp2(m - mn)
+        e = torch.exp2(s - mn)
+        pb = e.to(BF).float()
+        l = l * alpha + (pb if fault == "l_from_bf16" else e).sum(-1, keepdim=True)
+        if fault != "no_rescale":
+            o = o * alpha
+        o = o + pb @ v[:, :, k0:k0 + tile]
+        m = mn
+    lse = m + torch.log2(l)
+    if fault == "lse_natural":
+        lse = lse * kr.LN2
+    lse = lse.reshape(B, H, T)
+    if fault == "lse_bh_swapped":  # stored at [h * B + b]
+        lse = lse.transpose(0, 1)
+    return kr.attn_flat(o / l).to(BF), lse.reshape(B * H, T).contiguous()
+
+
+def emulate_attn_bwd(inp, out, lse, fault=None):
+    """fp32 emulation of the recomputing backward: P and dS packed to bf16 before the second
+    GEMMs, fp32 accumulation -> dqkv bf16 [B][T][3*H*64]."""
+    q, k, v = _heads32(inp["qkv"], AH)
+    B, H, T, _ = q.shape
+    o, do = kr.attn_rows(out, AH).float(), kr.attn_rows(inp["dout"], AH).float()
+    c = torch.tensor(kr.attn_c(ASC), dtype=torch.float32)
+    P = torch.exp2((q @ k.transpose(-1, -2)) * c - lse.view(B, H, T, 1))
+    delta = (do * o).sum(-1, keepdim=True)
+    if fault == "delta_wrong_row":
+        delta = delta.roll(1, 2)
+    dS = P * (do @ v.transpose(-1, -2) - delta)
+    Pb, dSb = P.to(BF).float(), dS.to(BF).float()
+    sc = 1.0 if fault == "dk_no_scale" else ASC
+    return kr._attn_pack3((dSb @ k) * ASC, (dSb.transpose(-1, -2) @ q) * sc, Pb.transpose(-1, -2) @ do).to(BF)
+
+
+@pytest.mark.parametrize("T", EMU_T)
+@pytest.mark.parametrize("family", kr.ATTN_FAMILIES)
+def test_attn_emulation_within_bounds(family, T):
+    """The unmodified fp32 emulation passes every family within the derived bounds (tiles of 64 and
+    of 32 keys, and the whole sequence at once): the references alone stay inside them."""
+    inp, fwd, out_r, lse_r, bwd = attn_case(family, T)
+    for tile in (64, 32, 512):
+        out, lse = emulate_attn_fwd(inp, tile)
+        kr.attn_check_fwd(inp, fwd, out, lse, AH, f"{family} T={T} tile={tile}")
+    kr.attn_check_bwd(inp, bwd, emulate_attn_bwd(inp, out_r, lse_r), AH, f"{family} T={T}")
+    if family == "counting":  # the closed form: 8 n_d / T
+        n = torch.zeros(AB, AH, 64, dtype=kr.F64)
+        for b in range(AB):
+            for h in range(AH):
+                n[b, h] = torch.bincount((torch.arange(T) + 5 * (b * AH + h)) % 64, minlength=64)
+        assert rel(fwd["out"].view(AB, T, AH, 64)[:, 3], 8 * n / T) < 1e-12
+
+
+def _rejects(check):
+    try:
+        check()
+    except AssertionError:
+        return True
+    return False
+
+
+# fault -> (forward or backward, the family named to reject it, the T at which it does)
+ATTN_FAULTS = {
+    "unmasked": ("fwd", "negative", 65),         # the padded key's score 0 beats every real one
+    "skip_key": ("fwd", "onehot", 65),           # the query that selects it gets another row (NaN: none)
+    "swap_v": ("fwd", "onehot", 65),
+    "no_rescale": ("fwd", "onehot", 65),         # query 0 selects key T - 1: the maximum arrives last
+    "l_from_bf16": ("fwd", "negative", 5),       # lse moves by ~2^-9 / sqrt(T), the bound is ~1e-4
+    "lse_natural": ("fwd", "counting", 65),
+    "lse_bh_swapped": ("fwd", "normal", 65),     # (onehot and counting have the same lse in every head)
+    "dk_no_scale": ("bwd", "normal", 65),
+    "delta_wrong_row": ("bwd", "onehot", 65),    # dP - delta no longer cancels: dQ, dK != 0
+}
+
+
+@pytest.mark.parametrize("fault", sorted(ATTN_FAULTS))
+def test_attn_seeded_fault_is_rejected(fault):
+    """Each fault, seeded alone into the emulation, is rejected by the family named for it."""
+    kind, family, T = ATTN_FAULTS[fault]
+    inp, fwd, out_r, lse_r, bwd = attn_case(family, T)
+    if kind == "fwd":
+        out, lse = emulate_attn_fwd(inp, 64, fault)
+        assert _rejects(lambda: kr.attn_check_fwd(inp, fwd, out, lse, AH, fault))
+        kr.attn_check_fwd(inp, fwd, *emulate_attn_fwd(inp, 64), AH, fault)
+    else:
+        assert _rejects(lambda: kr.attn_check_bwd(inp, bwd, emulate_attn_bwd(inp, out_r, lse_r, fault), AH, fault))
+        kr.attn_check_bwd(inp, bwd, emulate_attn_bwd(inp, out_r, lse_r), AH, fault)
+
+
+def emulate_cls(inp, o=None, lse=None):
+    """fp32 evaluation of the class-token attention: forward (o is None) -> (out bf16 [B][H*64],
+    lse fp32 [B*H]); backward from the given o and lse -> dqkv bf16 [B][T][3*H*64]."""
+    q, k, v = _heads32(inp["qkv"], AH)
+    B, H, T, _ = q.shape
+    q0 = q[:, :, :1] * 0.125
+    s = q0 @ k.transpose(-1, -2)
+    if o is None:
+        m = s.max(-1, keepdim=True).values
+        e = torch.exp(s - m)
+        l = e.sum(-1, keepdim=True)
+        return ((e / l) @ v).reshape(B, H * 64).to(BF), (m + torch.log(l)).reshape(B * H)
+    do = inp["dout"][:, 0].float().view(B, H, 1, 64)
+    P = torch.exp(s - lse.view(B, H, 1, 1))
+    dS = P * (do @ v.transpose(-1, -2) - (do * o.float().view(B, H, 1, 64)).sum(-1, keepdim=True))
+    dq = torch.zeros_like(q)
+    dq[:, :, :1] = (dS @ k) * 0.125
+    return kr._attn_pack3(dq, dS.transpose(-1, -2) * q0, P.transpose(-1, -2) * do).to(BF)
+
+
+def test_attn_cls_emulation_and_faults():
+    """The class-token checks accept an fp32 evaluation and reject an unwritten dq row, a dq of
+    another token that is not 0, and a log2-domain lse."""
+    for family in ("onehot", "onehot0", "counting", "negative", "normal"):
+        for T in (1, 33, 197):
+            what = f"{family} T={T}"
+            inp = kr.attn_inputs(family, AB, T, AH, kr.attn_seed(family, T), CPU)
+            f = kr.attn_cls_ref(inp["qkv"], AH)
+            out, lse = emulate_cls(inp)
+            kr.attn_check_cls_fwd(inp, f, out, lse, AH, what)
+            o_r, lse_r = f["out"].to(BF), f["lse"].to(torch.float32)
+            r = kr.attn_cls_ref(inp["qkv"], AH, inp["dout"][:, 0], o_r, lse_r)
+            good = emulate_cls(inp, o_r, lse_r)
+            kr.attn_check_cls_bwd(inp, r, good, AH, what)
+            if T > 1:
+                bad = good.clone()
+                bad.view(AB, T, 3, AH * 64)[1, T - 1, 0, 5] = float("nan")
+                assert _rejects(lambda: kr.attn_check_cls_bwd(inp, r, bad, AH, "poison"))
+                bad = good.clone()
+                bad.view(AB, T, 3, AH * 64)[0, 1, 0, 0] = 2.0 ** -100
+                assert _rejects(lambda: kr.attn_check_cls_bwd(inp, r, bad, AH, "nonzero"))
+                assert _rejects(lambda: kr.attn_check_cls_fwd(inp, f, out, lse / kr.LN2, AH, "log2 lse"))

@@ -529,6 +529,9 @@ def test_fused_qkv_attention(B, T, H):
     torch.cuda.synchronize()
     assert out.shape == ref.shape and out.dtype == torch.bfloat16
     assert nrmerr(out, ref) < 1e-2, nrmerr(out, ref)
+    # every element against the float64 reference within the derived bound (kernel_ref, "Attention")
+    f64ref = kr.attn_fwd_ref(qkv, H, 64 ** -0.5)
+    kr.assert_close(out.detach(), f64ref["out"], f64ref["out_bound"], "out")
     g, gr = xn.grad.view(B, T, 3, H * 64), x.grad.view(B, T, 3, H * 64)
     for i, name in enumerate("qkv"):
         e = nrmerr(g[:, :, i], gr[:, :, i])
