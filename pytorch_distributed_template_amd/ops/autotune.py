@@ -1,6 +1,6 @@
 """Tuned kernel choices: the table, the policy, the timing and the one selection protocol.
 
-Every GEMM, convolution and weight gradient of ``native_ops`` has several tile variants, and some
+Every GEMM, convolution and weight gradient of the ``native_ops`` package has several tile variants, and some
 fusions only pay on some geometries. The first eager call of a distinct geometry times the
 candidates with HIP events and keeps the fastest under a key (``<family>:<geometry>``); every later
 call is a dictionary lookup. No kernel binding lives here: a call site hands :func:`choose` its key,
@@ -17,7 +17,7 @@ Policy (:func:`tune_allowed`). ``PDT_AUTOTUNE=0`` or ``--deterministic`` (``PDT_
 no timing at all -- shipped/cached choices, else the site's fixed default, so every run and every
 rank picks the same variant (and the same split-K summation order). Never during a graph capture.
 World size > 1: ranks must not time variants independently (different choices per rank, stragglers
-inside the first backward): tuning is off unless ``native_ops.pretune_distributed`` runs -- rank 0
+inside the first backward): tuning is off unless ``native_ops.pretune_distributed`` (``native_ops/tuning.py``) runs -- rank 0
 tunes one step inside :func:`forced_tuning` and broadcasts its table; every rank :func:`adopt`s it,
 which freezes tuning for the rest of the process.
 

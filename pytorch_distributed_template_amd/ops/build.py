@@ -4,7 +4,7 @@
 ``csrc/*.hip`` with ``hipcc --offload-arch=gfx950 -O3`` into objects under
 ``build/hip`` and links ``pytorch_distributed_template_amd/_lib/libpdt_hip.so``.
 The library exposes a C ABI only (declared in ``csrc/pdt_api.h``) and is loaded
-with ctypes by ``ops/native_ops.py`` -- no torch headers, no hipify.
+with ctypes by ``ops/native_ops/lib.py`` -- no torch headers, no hipify.
 Incremental: an object is rebuilt only when its source or a header changed.
 """
 from __future__ import annotations

@@ -2,7 +2,7 @@
 
 Each function has two implementations:
   * ``native``: hand-written HIP/CDNA4 kernels (``csrc/*.hip``) wrapped in
-    ``torch.autograd.Function``s (see ``ops/native_ops.py``);
+    ``torch.autograd.Function``s (see ``ops/native_ops/``);
   * ``torch``: plain PyTorch ops -- used on CPU (gloo plumbing tests), as the
     fp32 reference in numerics tests, and as the "stock ROCm stack" baseline
     in ``bench.py --backend torch``.

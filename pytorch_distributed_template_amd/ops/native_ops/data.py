@@ -1,0 +1,100 @@
+"""raw kernel wrappers: synthetic images and the packed-image augmentation"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from .lib import _chk, _load, _p, _s, c_float
+
+
+def fill_uniform_(t: torch.Tensor, seed: int):
+    assert t.dtype == torch.bfloat16 and t.numel() % 8 == 0
+    _chk(_load().pdt_fill_uniform_bf16(_p(t), t.numel(), seed & 0xFFFFFFFF, _s()), "fill")
+    return t
+
+
+def synthetic_images_at(buf, idx, C, seed, labels, num_classes):
+    """Samples ``idx`` (int64 [B], device) of the index-addressable synthetic dataset into
+    ``buf`` (bf16 [B, H, W, Cp], channels >= C zeroed) and ``labels`` (int64 [B])."""
+    B, H, W, Cp = buf.shape
+    assert buf.dtype == torch.bfloat16 and buf.is_contiguous() and Cp % 4 == 0 and C <= Cp
+    assert idx.dtype == torch.int64 and idx.numel() == B and idx.device == buf.device
+    assert labels.dtype == torch.int64 and labels.numel() == B and labels.device == buf.device
+    _chk(_load().pdt_synth_images_bf16(_p(buf), _p(idx), B, H * W, C, Cp, seed & 0xFFFFFFFF, _p(labels),
+                                       int(num_classes), _s()), "synth_images")
+
+
+def crop_resize_normalize(src, idx, box, out, mean, std):
+    """The packed-image input pipeline in one launch (``csrc/image_aug.hip``): output ``b`` is the
+    crop ``box[b] = (y0, x0, h, w, flip)`` of stored image ``idx[b]`` (``idx`` None: image ``b``),
+    resized bilinearly (``align_corners=False``, no antialias) to ``S x S``, flipped horizontally
+    when ``flip``, and normalized ``(v / 255 - mean[c]) / std[c]``.
+
+    ``src`` uint8 [n, Hs, Ws, 3]; ``idx`` int64 [B] or None; ``box`` int32 [B, 5]; ``out`` bf16
+    [B, S, S, Cp] (channel 3 is written as 0); all on one device. ``mean`` / ``std``: 3 floats.
+    The kernel trusts the boxes and indices: validate them on the host (``data/packed.py``)."""
+    assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and src.is_contiguous()
+    assert out.dtype == torch.bfloat16 and out.dim() == 4 and out.is_contiguous() and out.device == src.device
+    B, S, S2, Cp = out.shape
+    assert S == S2 and Cp % 4 == 0 and B > 0
+    assert box.dtype == torch.int32 and tuple(box.shape) == (B, 5) and box.is_contiguous() and box.device == src.device
+    if idx is not None:
+        assert idx.dtype == torch.int64 and tuple(idx.shape) == (B,) and idx.is_contiguous() \
+            and idx.device == src.device
+    else:
+        assert src.shape[0] >= B
+    assert len(mean) == 3 and len(std) == 3 and all(float(s) > 0 for s in std)
+    m = (c_float * 3)(*[float(v) for v in mean])
+    inv = (c_float * 3)(*[1.0 / float(v) for v in std])
+    n, Hs, Ws, _ = src.shape
+    _chk(_load().pdt_crop_resize_norm_u8_bf16(_p(src), Hs, Ws, _p(idx), _p(box), _p(out), B, S, Cp,
+                                              ctypes.addressof(m), ctypes.addressof(inv), _s()), "crop_resize_norm")
+
+
+def crop_resize_normalize_mix(src, idx, box, pidx, pbox, rect, w_own, out, mean, std):
+    """:func:`crop_resize_normalize` with Mixup / CutMix in the same launch: output ``b`` is mixed
+    with its partner's augmented view -- the crop ``pbox[b]`` (the partner's own box and flip) of
+    stored image ``pidx[b]``. Inside the rectangle ``rect[b] = (y0, x0, y1, x1)`` (half-open,
+    output coordinates; empty when ``y0 == y1`` or ``x0 == x1``) a pixel is the partner's; outside
+    it is the own one when ``w_own[b] == 1``, else ``w_own * own + (1 - w_own) * partner``, formed
+    in fp32 before the normalization and the one rounding to bf16.
+
+    ``pidx`` int64 [B]; ``pbox`` int32 [B, 5]; ``rect`` int32 [B, 4] inside ``[0, S]^2``; ``w_own``
+    float32 [B] in [0, 1]; the rest as in :func:`crop_resize_normalize`. The kernel trusts them
+    all: validate on the host (``data/packed.py``: ``validate_boxes``, ``validate_mix``)."""
+    assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and src.is_contiguous()
+    assert out.dtype == torch.bfloat16 and out.dim() == 4 and out.is_contiguous() and out.device == src.device
+    B, S, S2, Cp = out.shape
+    assert S == S2 and Cp % 4 == 0 and B > 0
+    assert box.dtype == torch.int32 and tuple(box.shape) == (B, 5) and box.is_contiguous() and box.device == src.device
+    if idx is not None:
+        assert idx.dtype == torch.int64 and tuple(idx.shape) == (B,) and idx.is_contiguous() \
+            and idx.device == src.device
+    else:
+        assert src.shape[0] >= B
+    assert pidx is not None and pidx.dtype == torch.int64 and tuple(pidx.shape) == (B,) and pidx.is_contiguous() \
+        and pidx.device == src.device
+    assert pbox.dtype == torch.int32 and tuple(pbox.shape) == (B, 5) and pbox.is_contiguous() \
+        and pbox.device == src.device
+    assert rect.dtype == torch.int32 and tuple(rect.shape) == (B, 4) and rect.is_contiguous() \
+        and rect.device == src.device
+    assert w_own.dtype == torch.float32 and tuple(w_own.shape) == (B,) and w_own.is_contiguous() \
+        and w_own.device == src.device
+    assert len(mean) == 3 and len(std) == 3 and all(float(s) > 0 for s in std)
+    m = (c_float * 3)(*[float(v) for v in mean])
+    inv = (c_float * 3)(*[1.0 / float(v) for v in std])
+    n, Hs, Ws, _ = src.shape
+    _chk(_load().pdt_crop_resize_norm_mix_u8_bf16(_p(src), Hs, Ws, _p(idx), _p(box), _p(pidx), _p(pbox), _p(rect),
+                                                  _p(w_own), _p(out), B, S, Cp, ctypes.addressof(m),
+                                                  ctypes.addressof(inv), _s()), "crop_resize_norm_mix")
+
+
+def synthetic_images(shape, dtype, device, seed=0, channels_last=True):
+    n, c, h, w = shape
+    if channels_last:
+        x = torch.empty(shape, dtype=torch.bfloat16, device=device, memory_format=torch.channels_last)
+    else:
+        x = torch.empty(shape, dtype=torch.bfloat16, device=device)
+    fill_uniform_(x, seed)
+    return x if dtype == torch.bfloat16 else x.to(dtype)

@@ -1,5 +1,5 @@
 """The kernel library's C ABI is written once, in ``csrc/pdt_api.h``: the header, the definitions
-in ``csrc/*.hip``, the ctypes table ``ops/native_ops.py`` derives from the header, and the Python
+in ``csrc/*.hip``, the ctypes table ``ops/native_ops/lib.py`` derives from the header, and the Python
 call sites agree. No GPU; only the last test needs the built library."""
 import ctypes
 import re

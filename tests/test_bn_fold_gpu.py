@@ -153,7 +153,7 @@ def test_bottleneck_chain_fold_matches_unfolded(monkeypatch, train, force):
     LDS-DMA 128x128) instead of the tuner's choice, so the 1x1 and 3x3 folds (forward modes
     with and without residual, backward modes 2 and 3) all run whatever the timings say."""
     if force is not None:
-        monkeypatch.setattr(no, "_ax_select", lambda key, run, run_ref=None: force)
+        monkeypatch.setattr(no.bn_unit, "_ax_select", lambda key, run, run_ref=None: force)
     from pytorch_distributed_template_amd.ops import fused
     torch.manual_seed(11)
     net = _chain()
@@ -274,7 +274,7 @@ def test_dgrad_epilogue_second_unit_partials(monkeypatch, v, with_add):
     m3, md = torch.randn(Cin, device="cuda") * 0.1, torch.randn(Cin, device="cuda") * 0.1
     mask = torch.randint(0, 256, (y3.numel() // 8,), dtype=torch.uint8, device="cuda")
     u3, ud = _FakeUnit(y3, m3), _FakeUnit(yd, md, relu=False)
-    monkeypatch.setattr(no, "_select_bnb_variant", lambda *a, **k: v)
+    monkeypatch.setattr(no.conv, "_select_bnb_variant", lambda *a, **k: v)
     g = {"KH": 1, "KW": 1, "sh": 1, "sw": 1, "ph": 0, "pw": 0, "Ho": H, "Wo": H}
     add = _cl(torch.randn(N, Cin, H, H, device="cuda").to(torch.bfloat16)) if with_add else None
     dx, pre = no._conv_dgrad(dy, w, N, H, H, Cin, Cm, g, addend=add, bnb_unit=u3, bnb_mask=mask, bnb_unit2=ud)

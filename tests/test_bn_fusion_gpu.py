@@ -1,6 +1,6 @@
 """BatchNorm-backward reduction fused into the data-gradient GEMM epilogue
 (``BnbArgs`` in csrc/conv_igemm.hip, ``_Bottleneck.backward`` in
-ops/native_ops.py): fused vs the separate reduce pass vs an fp32 PyTorch
+ops/native_ops/bottleneck.py): fused vs the separate reduce pass vs an fp32 PyTorch
 reference of the same ResNet stage. Run on an MI355X."""
 import pytest
 import torch

@@ -858,7 +858,7 @@ def test_cast_fp8_delayed_colsum(rows, cols, fmt):
 
 def test_linear_wgrad_bias_without_param():
     """_linear_wgrad(..., with_bias=True) without a bias tensor: the bias-gradient buffer is
-    allocated on the GPU (ops/native_ops.py _grad_buf). With device=None it landed on the host
+    allocated on the GPU (ops/native_ops/lib.py _grad_buf). With device=None it landed on the host
     and the weight-gradient kernel wrote through a host pointer -- the illegal access that
     faulted round 5's r5z variant sweep."""
     torch.manual_seed(3)
@@ -875,7 +875,7 @@ def test_linear_wgrad_bias_without_param():
 
 def test_vit_ln_codes_only_output_bit_identical(monkeypatch):
     """fp8 ViT with the LayerNorm outputs written as e4m3 codes only (their consumers, qkv and
-    fc1, read nothing else: ops/native_ops.py _ln_codes_only) against the same step with the bf16
+    fc1, read nothing else: ops/native_ops/layernorm.py _ln_codes_only) against the same step with the bf16
     outputs written too: loss and every parameter gradient bit-identical from the same weights
     and fp8 scaling state, and the codes-only launches actually taken."""
     from pytorch_distributed_template_amd.models.vit import VisionTransformer
