@@ -1,25 +1,15 @@
 // Multi-tensor fused optimizer steps (one launch for every parameter tensor).
-// Reference: torch.optim.Adam(amsgrad) step (/root/reference/config/config.json:38-45,
-// /root/reference/trainer/trainer.py:58); SGD-momentum is the ResNet recipe.
+// Reference: the torch.optim.Adam(amsgrad) step of the reference project (config/config.json,
+// "optimizer"; stepped once per batch in trainer/trainer.py); SGD-momentum is the ResNet recipe.
 //
-// Work list: the host builds, once per parameter set, a device table of
-// chunks {tensor id, element offset, length}; each workgroup walks chunks with
-// a grid-stride loop and reads the tensor's pointers from a pointer table.
+// Work list (csrc/optim_common.h): each workgroup walks chunks {tensor id, element offset,
+// length} with a grid-stride loop and reads the tensor's pointers from a pointer table.
 // fp32 master params / grads / states; optionally a bf16 shadow copy of each
 // param is written in the same pass (the copy the bf16 conv/GEMM kernels read),
 // so no separate cast kernel runs per step.
-#include "pdt_common.h"
+#include "optim_common.h"
 
 namespace {
-
-struct Chunk {
-  int tensor;
-  int pad;
-  long offset;
-  long len;
-};
-
-constexpr int NT = 256;
 
 // SGD (torch semantics): g += wd*p; buf = mom*buf + (1-damp)*g (buf = g on
 // first step); g = nesterov ? g + mom*buf : buf; p -= lr*g
@@ -42,43 +32,35 @@ __global__ void sgd_kernel(const Chunk* __restrict__ chunks, int nchunks, float*
     const Chunk ch = chunks[c];
     float* p = params[ch.tensor] + ch.offset;
     const float* g = grads[ch.tensor] + ch.offset;
-    float* b = bufs ? (bufs[ch.tensor] ? bufs[ch.tensor] + ch.offset : nullptr) : nullptr;
-    u16* sh = shadows ? (shadows[ch.tensor] ? shadows[ch.tensor] + ch.offset : nullptr) : nullptr;
+    float* b = role_ptr(bufs, ch.tensor, ch.offset);
+    u16* sh = role_ptr(shadows, ch.tensor, ch.offset);
     const bool hb = b != nullptr;
-    long i0 = 0;
     // 16-B vector path when every stream is aligned (gradients can be unaligned views
     // into DDP's buckets): 4 elements per lane, all loads issued before the math
     const uintptr_t al = (uintptr_t)p | (uintptr_t)g | (hb ? (uintptr_t)b : 0);
-    if ((al & 15) == 0 && (!sh || ((uintptr_t)sh & 7) == 0)) {
-      const long n4 = ch.len >> 2;
-      for (long j = threadIdx.x; j < n4; j += NT) {
-        const f32x4 gv = reinterpret_cast<const f32x4*>(g)[j];
-        f32x4 pv = reinterpret_cast<const f32x4*>(p)[j];
-        f32x4 bv = hb ? reinterpret_cast<const f32x4*>(b)[j] : f32x4{0.f, 0.f, 0.f, 0.f};
+    walk_chunk(
+        ch.len, (al & 15) == 0 && (!sh || ((uintptr_t)sh & 7) == 0),
+        [&](long j) {
+          const f32x4 gv = reinterpret_cast<const f32x4*>(g)[j];
+          f32x4 pv = reinterpret_cast<const f32x4*>(p)[j];
+          f32x4 bv = hb ? reinterpret_cast<const f32x4*>(b)[j] : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float be = bv[e];
-          pv[e] = upd(gv[e], pv[e], be, hb);
-          bv[e] = be;
-        }
-        reinterpret_cast<f32x4*>(p)[j] = pv;
-        if (hb && momentum != 0.f) reinterpret_cast<f32x4*>(b)[j] = bv;
-        if (sh) {
-          uint2 w;
-          w.x = pack2bf(pv[0], pv[1]);
-          w.y = pack2bf(pv[2], pv[3]);
-          reinterpret_cast<uint2*>(sh)[j] = w;
-        }
-      }
-      i0 = n4 << 2;
-    }
-    for (long i = i0 + threadIdx.x; i < ch.len; i += NT) {
-      float bi = hb ? b[i] : 0.f;
-      const float pi = upd(g[i], p[i], bi, hb);
-      if (hb && momentum != 0.f) b[i] = bi;
-      p[i] = pi;
-      if (sh) sh[i] = f2bf(pi);
-    }
+          for (int e = 0; e < 4; ++e) {
+            float be = bv[e];
+            pv[e] = upd(gv[e], pv[e], be, hb);
+            bv[e] = be;
+          }
+          reinterpret_cast<f32x4*>(p)[j] = pv;
+          if (hb && momentum != 0.f) reinterpret_cast<f32x4*>(b)[j] = bv;
+          if (sh) store_shadow4(sh, j, pv);
+        },
+        [&](long i) {
+          float bi = hb ? b[i] : 0.f;
+          const float pi = upd(g[i], p[i], bi, hb);
+          if (hb && momentum != 0.f) b[i] = bi;
+          p[i] = pi;
+          if (sh) sh[i] = f2bf(pi);
+        });
   }
 }
 
@@ -102,7 +84,7 @@ __global__ void adam_kernel(const Chunk* __restrict__ chunks, int nchunks, float
     float* m = exp_avg[ch.tensor] + ch.offset;
     float* v = exp_avg_sq[ch.tensor] + ch.offset;
     float* vm = max_sq ? max_sq[ch.tensor] + ch.offset : nullptr;
-    u16* sh = shadows ? (shadows[ch.tensor] ? shadows[ch.tensor] + ch.offset : nullptr) : nullptr;
+    u16* sh = role_ptr(shadows, ch.tensor, ch.offset);
     for (long i = threadIdx.x; i < ch.len; i += NT) {
       float gi = g[i] * grad_scale;
       float pi = p[i];
@@ -126,8 +108,6 @@ __global__ void adam_kernel(const Chunk* __restrict__ chunks, int nchunks, float
     }
   }
 }
-
-int grid_for(int n) { return n < 2048 ? (n < 1 ? 1 : n) : 2048; }
 
 // capturable Adam: t += 1 on the device, ahead of the step kernel in the same stream
 __global__ void opt_tick_kernel(float* dev) {

@@ -1,9 +1,9 @@
 // Layer-wise adaptive optimizers (LARS, LAMB) with on-device gradient-norm clipping, and the
 // deterministic multi-tensor L2 norm they are built on.
 //
-// Same work list as csrc/optim.hip: a 24-byte Chunk {tensor, pad, offset, len} table, one
-// pointer table per role, workgroups of 256 threads walking chunks grid-stride. Two more
-// device tables, built by the host once per parameter set:
+// Same work list as csrc/optim.hip (csrc/optim_common.h): a 24-byte Chunk {tensor, pad, offset,
+// len} table, one pointer table per role, workgroups of 256 threads walking chunks grid-stride.
+// Two more device tables, built by the host once per parameter set:
 //   chunk_begin[n_tensors + 1]  a tensor's chunks are consecutive: [chunk_begin[t], chunk_begin[t + 1])
 //   flags[n_tensors]            bit 0: layer-wise adaptation and weight decay apply
 //
@@ -20,34 +20,11 @@
 //
 // All arithmetic is fp32 on fp32 masters; the bf16 shadow of each parameter is written in the
 // pass that updates it, as sgd_kernel does.
-#include "pdt_common.h"
+#include "optim_common.h"
 
 namespace {
 
-struct Chunk {
-  int tensor;
-  int pad;
-  long offset;
-  long len;
-};
-
-constexpr int NT = 256;
 constexpr int NW = NT / 64;
-
-int grid_for(int n) { return n < 2048 ? (n < 1 ? 1 : n) : 2048; }
-
-// walk one chunk: 4 elements per lane (16-B loads / stores) while `aligned`, scalar otherwise
-// and for the tail
-template <typename F4, typename F1>
-__device__ __forceinline__ void walk_chunk(long len, bool aligned, F4 f4, F1 f1) {
-  long i0 = 0;
-  if (aligned) {
-    const long n4 = len >> 2;
-    for (long j = threadIdx.x; j < n4; j += NT) f4(j);
-    i0 = n4 << 2;
-  }
-  for (long i = i0 + threadIdx.x; i < len; i += NT) f1(i);
-}
 
 // workgroup sums of two per-lane values in a fixed order: lanes by warp_sum, then the four
 // waves left to right; thread 0 stores them to out[0] (and out[1] when `two`). Every thread of
@@ -163,8 +140,8 @@ __global__ void lars_kernel(const Chunk* __restrict__ chunks, int nchunks, float
     const int t = ch.tensor;
     float* p = params[t] + ch.offset;
     const float* g = grads[t] + ch.offset;
-    float* b = bufs ? (bufs[t] ? bufs[t] + ch.offset : nullptr) : nullptr;
-    u16* sh = shadows ? (shadows[t] ? shadows[t] + ch.offset : nullptr) : nullptr;
+    float* b = role_ptr(bufs, t, ch.offset);
+    u16* sh = role_ptr(shadows, t, ch.offset);
     const bool hb = b != nullptr;
     float q = 1.f, wdt = 0.f;
     if (flags[t] & 1) {
@@ -196,12 +173,7 @@ __global__ void lars_kernel(const Chunk* __restrict__ chunks, int nchunks, float
           }
           reinterpret_cast<f32x4*>(p)[j] = pv;
           if (hb) reinterpret_cast<f32x4*>(b)[j] = bv;
-          if (sh) {
-            uint2 w;
-            w.x = pack2bf(pv[0], pv[1]);
-            w.y = pack2bf(pv[2], pv[3]);
-            reinterpret_cast<uint2*>(sh)[j] = w;
-          }
+          if (sh) store_shadow4(sh, j, pv);
         },
         [&](long i) {
           float bi = hb ? b[i] : 0.f;
@@ -312,7 +284,7 @@ __global__ void lamb_stage2_kernel(const Chunk* __restrict__ chunks, int nchunks
     float* p = params[t] + ch.offset;
     const float* m = exp_avg[t] + ch.offset;
     const float* v = exp_avg_sq[t] + ch.offset;
-    u16* sh = shadows ? (shadows[t] ? shadows[t] + ch.offset : nullptr) : nullptr;
+    u16* sh = role_ptr(shadows, t, ch.offset);
     float r = 1.f, wdt = 0.f;
     if (flags[t] & 1) {
       const float un = norms[t], wn = norms[(long)nt + t];
@@ -330,12 +302,7 @@ __global__ void lamb_stage2_kernel(const Chunk* __restrict__ chunks, int nchunks
 #pragma unroll
           for (int e = 0; e < 4; ++e) pv[e] -= step * lamb_u(mv[e], vv[e], pv[e], bc1, bc2, eps, wdt);
           reinterpret_cast<f32x4*>(p)[j] = pv;
-          if (sh) {
-            uint2 w;
-            w.x = pack2bf(pv[0], pv[1]);
-            w.y = pack2bf(pv[2], pv[3]);
-            reinterpret_cast<uint2*>(sh)[j] = w;
-          }
+          if (sh) store_shadow4(sh, j, pv);
         },
         [&](long i) {
           const float pi = p[i] - step * lamb_u(m[i], v[i], p[i], bc1, bc2, eps, wdt);

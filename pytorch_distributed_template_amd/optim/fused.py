@@ -1,8 +1,8 @@
 """Multi-tensor fused SGD / Adam(W) (+AMSGrad) on MI355X.
 
-Reference optimizer: ``torch.optim.Adam(lr=1e-3, weight_decay=0, amsgrad=True)``
-(``/root/reference/config/config.json:38-45``), stepped once per batch at
-``trainer/trainer.py:58``. Semantics match torch.optim exactly (tested against
+Reference optimizer: ``torch.optim.Adam(lr=1e-3, weight_decay=0, amsgrad=True)`` (the
+``optimizer`` entry of the reference project's ``config/config.json``), stepped once per batch
+in its ``trainer/trainer.py``. Semantics match torch.optim exactly (tested against
 it); the state_dict format is torch's (``momentum_buffer`` / ``exp_avg`` /
 ``exp_avg_sq`` / ``max_exp_avg_sq`` / ``step``), so checkpoints interchange
 with the torch optimizers of the same name.
@@ -31,10 +31,11 @@ reloaded into torch.optim would apply different bias corrections.
 layer-wise optimizers of the large-batch recipes, with global gradient-norm clipping on the
 device; they are built on ``multi_tensor_l2norm``, a deterministic per-tensor L2 norm whose
 results stay in device memory.
+
+All five share ``_FusedBase.step()`` and what it needs (``csrc/optim_common.h`` is the kernels'
+counterpart); a class adds its state, its pointer roles, its launches and its torch path.
 """
 from __future__ import annotations
-
-import ctypes
 
 import os
 
@@ -44,6 +45,19 @@ from torch.optim import Optimizer
 # elements per work-list chunk (one workgroup walks one chunk; PDT_OPT_CHUNK overrides):
 # 32768 -- ResNet-50 FusedSGD step 248 us vs 289 us at 65536 (profiles/optim_chunk_round2.txt)
 CHUNK = int(os.environ.get("PDT_OPT_CHUNK", "32768"))
+
+
+def _ops():
+    """``ops.native_ops``, imported on first use: this module must import where no kernel
+    library is built."""
+    from ..ops import native_ops
+    return native_ops
+
+
+def _call(entry, *args, what=None):
+    """Call the kernel library's ``pdt_<entry>``; an error code raises (naming ``what``)."""
+    ops = _ops()
+    ops._chk(getattr(ops._load(), "pdt_" + entry)(*args), what or entry)
 
 
 def _bump_versions(params):
@@ -73,9 +87,7 @@ class _Plan:
     buffers at new addresses."""
 
     def __init__(self, params, device):
-        from ..ops import native_ops
-        lib = native_ops._load()
-        sz = lib.pdt_chunk_struct_size()
+        sz = _ops()._load().pdt_chunk_struct_size()
         assert sz == 24, sz
         import numpy as np
         sizes = [p.numel() for p in params]
@@ -110,14 +122,33 @@ class _Plan:
 
 
 def _native_ok(params):
-    from ..ops import native_ops
-    return (len(params) > 0 and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous(
-        memory_format=torch.channels_last if p.dim() == 4 else torch.contiguous_format) or
-        (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()) for p in params)
-        and native_ops.available())
+    return (len(params) > 0 and all(
+        p.is_cuda and p.dtype == torch.float32 and (
+            p.is_contiguous() or (p.dim() == 4 and p.is_contiguous(memory_format=torch.channels_last)))
+        for p in params) and _ops().available())
+
+
+def _dense_grads(params):
+    """fp32 gradients laid out like their parameters (what the kernels index). torch refuses to
+    assign a gradient of another dtype than its parameter's, but a swap of ``p.grad.data`` (or of
+    ``p.data``) leaves one behind: hence the ``float()``."""
+    grads = [p.grad if p.grad.dtype == torch.float32 else p.grad.float() for p in params]
+    return [g if g.stride() == p.stride() else g.contiguous(memory_format=torch.channels_last
+                                                             if p.dim() == 4 else torch.contiguous_format)
+            for g, p in zip(grads, params)]
 
 
 class _FusedBase(Optimizer):
+    """What the five optimizers share: the frame of ``step()``, plans, shadows, device scalars.
+
+    A subclass has ``_native_step(work)`` and ``_torch_step(work)``; ``work`` is a list of
+    ``(group index, group, its parameters with a gradient)``. Without ``whole_step_fallback``
+    every group takes the native path if it passes ``_native_ok`` and the torch path if not
+    (``work`` then holds one group per call); with it, one failing group sends the whole step
+    down the torch path."""
+    whole_step_fallback = False
+    dev_width = 2  # floats of a group's device scalars
+
     def __init__(self, params, defaults, write_bf16_shadow=True, capturable=False):
         super().__init__(params, defaults)
         self.write_bf16_shadow = write_bf16_shadow
@@ -128,14 +159,87 @@ class _FusedBase(Optimizer):
         self._dev_lr = {}   # the lr last written into it
         self._grad_sets = {}  # capturable Adam: group index -> ids of the params stepped first
 
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._step_prologue()
+        work = []
+        for gi, group in enumerate(self.param_groups):
+            params = [p for p in group["params"] if p.grad is not None]
+            if params:
+                work.append((gi, group, params))
+        parts = [work] if self.whole_step_fallback else [[item] for item in work]
+        for part in parts if work else []:
+            if all(_native_ok(params) for _, _, params in part):
+                self._native_step(part)
+            else:
+                self._torch_step(part)
+        return loss
+
     def _dev_scalars(self, gi, group, device, t0=0.0):
-        """The group's device [lr, t] (created from the host values on first use)."""
+        """The group's device ``[lr, t]`` and, up to ``dev_width``, the floats a tick kernel
+        writes after them (created from the host values on first use)."""
         d = self._dev.get(gi)
         if d is None:
-            d = torch.tensor([float(group["lr"]), float(t0)], dtype=torch.float32, device=device)
+            d = torch.tensor([float(group["lr"]), float(t0)] + [1.0] * (self.dev_width - 2), dtype=torch.float32,
+                             device=device)
             self._dev[gi] = d
             self._dev_lr[gi] = float(group["lr"])
         return d
+
+    def _write_back_steps(self):
+        """Capturable mode: set each parameter's ``step`` from its group's device step count
+        (replayed graphs advance only that), so that ``state_dict()`` stays torch's."""
+        if not self.capturable:
+            return
+        for gi, group in enumerate(self.param_groups):
+            d = self._dev.get(gi)
+            if d is None:
+                continue
+            t = float(d[1].item())
+            for p in group["params"]:
+                if p in self.state and "step" in self.state[p]:
+                    self.state[p]["step"] = torch.tensor(t)
+
+    def _adam_moments(self, name, work, dev_step):
+        """Adam's state for ``work``: created (``max_exp_avg_sq`` too in an ``amsgrad`` group) on a
+        parameter's first step, and ``step`` advanced unless the device counts it (``dev_step``:
+        the parameters with gradients must then be the same on every step). Returns this step's
+        ``{group index: (bc1, bc2)}``."""
+        bcs = {}
+        for gi, group, params in work:
+            if dev_step:
+                key = tuple(id(p) for p in params)
+                seen = self._grad_sets.setdefault(gi, key)
+                if seen != key:
+                    raise RuntimeError(
+                        f"capturable {name}: the set of parameters with gradients changed between steps "
+                        f"(group {gi}: {len(seen)} -> {len(key)} params); the group's single device step "
+                        "count requires every parameter to receive a gradient on every step")
+            for p in params:
+                st = self.state[p]
+                if len(st) == 0:
+                    st["step"] = torch.tensor(0.0)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    if group.get("amsgrad"):
+                        st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                if not dev_step:  # (capturable: the device count is the step, see _write_back_steps)
+                    st["step"] += 1
+            b1, b2 = group["betas"]
+            step = float(self.state[params[0]]["step"]) if not dev_step else 1.0
+            bcs[gi] = (1 - b1 ** step, 1 - b2 ** step)
+        return bcs
+
+    def _finish(self, params, shadows):
+        _bump_versions(params)
+        if self.write_bf16_shadow:
+            register_shadow = _ops().register_shadow
+            for p, s in zip(params, shadows):
+                register_shadow(p, s)
 
     @torch.no_grad()
     def sync_shadows(self):
@@ -149,14 +253,13 @@ class _FusedBase(Optimizer):
         capture, the captured forward reads the shadows the captured ``step()`` rewrites."""
         if not self.write_bf16_shadow:
             return
-        from ..ops import native_ops
         for group in self.param_groups:
             for p in group["params"]:
                 sh = self._shadows.get(id(p))
                 if sh is None or sh.data_ptr() == 0 or sh.shape != p.shape:
                     continue
                 sh.copy_(p.detach())
-                native_ops.register_shadow(p, sh)
+                _ops().register_shadow(p, sh)
 
     def refresh_scalars(self):
         """Write each group's current lr into its device scalars (capturable mode): call it
@@ -231,70 +334,49 @@ class FusedSGD(_FusedBase):
                         nesterov=nesterov)
         super().__init__(params, defaults, write_bf16_shadow, capturable)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        self._step_prologue()
-        for gi, group in enumerate(self.param_groups):
-            params = [p for p in group["params"] if p.grad is not None]
-            if not params:
-                continue
-            if not _native_ok(params):
-                self._torch_step(group, params)
-                continue
-            from ..ops import native_ops
+    def _native_step(self, work):
+        for gi, group, params in work:
+            mom = group["momentum"] != 0
+            # ONE first-step flag for the group: a buffer created on a later step makes the
+            # kernel take buf = g for every tensor of the group on that step
             first = False
             bufs = []
             for p in params:
                 st = self.state[p]
-                if group["momentum"] != 0:
+                if mom:
                     if "momentum_buffer" not in st or st["momentum_buffer"] is None:
                         st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                         first = True
                     bufs.append(st["momentum_buffer"])
                 else:
                     bufs.append(None)
-            grads = [p.grad if p.grad.dtype == torch.float32 else p.grad.float() for p in params]
-            grads = [g if g.stride() == p.stride() else g.contiguous(memory_format=torch.channels_last
-                                                                     if p.dim() == 4 else torch.contiguous_format)
-                     for g, p in zip(grads, params)]
             shadows = [self._shadow(p) for p in params]
-            roles = {"p": params, "g": grads, "b": bufs if group["momentum"] != 0 else [None] * len(params),
-                     "s": shadows if self.write_bf16_shadow else [None] * len(params)}
+            roles = {"p": params, "g": _dense_grads(params), "b": bufs, "s": shadows}
             plan = self._plan(gi, params, roles, params[0].device)
             dev = self._dev_scalars(gi, group, params[0].device) if self.capturable else None
-            rc = native_ops._load().pdt_sgd_step2(
-                plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("g"),
-                plan.ptr("b") if group["momentum"] != 0 else None,
-                plan.ptr("s") if self.write_bf16_shadow else None,
-                float(group["lr"]), float(group["momentum"]), float(group["dampening"]),
-                float(group["weight_decay"]), int(group["nesterov"]), int(first), 1.0,
-                dev.data_ptr() if dev is not None else None, self._stream())
-            native_ops._chk(rc, "sgd_step")
-            _bump_versions(params)
-            if self.write_bf16_shadow:
-                for p, s in zip(params, shadows):
-                    native_ops.register_shadow(p, s)
-        return loss
+            _call("sgd_step2", plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("g"),
+                  plan.ptr("b") if mom else None, plan.ptr("s") if self.write_bf16_shadow else None,
+                  float(group["lr"]), float(group["momentum"]), float(group["dampening"]),
+                  float(group["weight_decay"]), int(group["nesterov"]), int(first), 1.0,
+                  dev.data_ptr() if dev is not None else None, self._stream(), what="sgd_step")
+            self._finish(params, shadows)
 
-    def _torch_step(self, group, params):
-        for p in params:
-            g = p.grad
-            if group["weight_decay"] != 0:
-                g = g.add(p, alpha=group["weight_decay"])
-            if group["momentum"] != 0:
-                st = self.state[p]
-                buf = st.get("momentum_buffer")
-                if buf is None:
-                    buf = torch.clone(g).detach()
-                    st["momentum_buffer"] = buf
-                else:
-                    buf.mul_(group["momentum"]).add_(g, alpha=1 - group["dampening"])
-                g = g.add(buf, alpha=group["momentum"]) if group["nesterov"] else buf
-            p.add_(g, alpha=-group["lr"])
+    def _torch_step(self, work):
+        for _, group, params in work:
+            for p in params:
+                g = p.grad
+                if group["weight_decay"] != 0:
+                    g = g.add(p, alpha=group["weight_decay"])
+                if group["momentum"] != 0:
+                    st = self.state[p]
+                    buf = st.get("momentum_buffer")
+                    if buf is None:
+                        buf = torch.clone(g).detach()
+                        st["momentum_buffer"] = buf
+                    else:
+                        buf.mul_(group["momentum"]).add_(g, alpha=1 - group["dampening"])
+                    g = g.add(buf, alpha=group["momentum"]) if group["nesterov"] else buf
+                p.add_(g, alpha=-group["lr"])
 
 
 class FusedAdam(_FusedBase):
@@ -307,102 +389,53 @@ class FusedAdam(_FusedBase):
         super().__init__(params, defaults, write_bf16_shadow, capturable)
 
     def state_dict(self):
-        """torch's format; in capturable mode each parameter's ``step`` is first set from the
-        group's device step count (replayed graphs advance only that)."""
-        if self.capturable:
-            for gi, group in enumerate(self.param_groups):
-                d = self._dev.get(gi)
-                if d is None:
-                    continue
-                t = float(d[1].item())
-                for p in group["params"]:
-                    if p in self.state and "step" in self.state[p]:
-                        self.state[p]["step"] = torch.tensor(t)
+        """torch's format (in capturable mode after ``_write_back_steps()``)."""
+        self._write_back_steps()
         return super().state_dict()
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        self._step_prologue()
-        for gi, group in enumerate(self.param_groups):
-            params = [p for p in group["params"] if p.grad is not None]
-            if not params:
-                continue
+    def _native_step(self, work):
+        dev_step = self.capturable
+        bcs = self._adam_moments("FusedAdam", work, dev_step)
+        for gi, group, params in work:
             b1, b2 = group["betas"]
-            native = _native_ok(params)
-            dev_step = self.capturable and native
-            if dev_step:
-                key = tuple(id(p) for p in params)
-                seen = self._grad_sets.setdefault(gi, key)
-                if seen != key:
-                    raise RuntimeError(
-                        "capturable FusedAdam: the set of parameters with gradients changed between steps "
-                        f"(group {gi}: {len(seen)} -> {len(key)} params); the group's single device step "
-                        "count requires every parameter to receive a gradient on every step")
-            for p in params:
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = torch.tensor(0.0)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    if group["amsgrad"]:
-                        st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                if not dev_step:  # (capturable: the device count is the step, see state_dict)
-                    st["step"] += 1
-            step = float(self.state[params[0]]["step"]) if not dev_step else 1.0
-            bc1 = 1 - b1 ** step
-            bc2 = 1 - b2 ** step
-            if not native:
-                self._torch_step(group, params, bc1, bc2)
-                continue
-            from ..ops import native_ops
-            grads = [p.grad if p.grad.dtype == torch.float32 else p.grad.float() for p in params]
-            grads = [g if g.stride() == p.stride() else g.contiguous(memory_format=torch.channels_last
-                                                                     if p.dim() == 4 else torch.contiguous_format)
-                     for g, p in zip(grads, params)]
+            bc1, bc2 = bcs[gi]
             shadows = [self._shadow(p) for p in params]
-            roles = {"p": params, "g": grads, "m": [self.state[p]["exp_avg"] for p in params],
+            roles = {"p": params, "g": _dense_grads(params), "m": [self.state[p]["exp_avg"] for p in params],
                      "v": [self.state[p]["exp_avg_sq"] for p in params],
-                     "vm": [self.state[p].get("max_exp_avg_sq") for p in params] if group["amsgrad"]
-                     else [None] * len(params),
-                     "s": shadows if self.write_bf16_shadow else [None] * len(params)}
+                     "vm": [self.state[p].get("max_exp_avg_sq") if group["amsgrad"] else None for p in params],
+                     "s": shadows}
             plan = self._plan(gi, params, roles, params[0].device)
             dev = self._dev_scalars(gi, group, params[0].device, t0=float(self.state[params[0]]["step"])) \
                 if dev_step else None
-            rc = native_ops._load().pdt_adam_step2(
-                plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("g"), plan.ptr("m"), plan.ptr("v"),
-                plan.ptr("vm") if group["amsgrad"] else None, plan.ptr("s") if self.write_bf16_shadow else None,
-                float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
-                int(self.decoupled), float(bc1), float(bc2), 1.0, dev.data_ptr() if dev is not None else None,
-                int(dev is not None), self._stream())
-            native_ops._chk(rc, "adam_step")
-            _bump_versions(params)
-            if self.write_bf16_shadow:
-                for p, s in zip(params, shadows):
-                    native_ops.register_shadow(p, s)
-        return loss
+            _call("adam_step2", plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("g"), plan.ptr("m"),
+                  plan.ptr("v"), plan.ptr("vm") if group["amsgrad"] else None,
+                  plan.ptr("s") if self.write_bf16_shadow else None, float(group["lr"]), float(b1), float(b2),
+                  float(group["eps"]), float(group["weight_decay"]), int(self.decoupled), float(bc1), float(bc2), 1.0,
+                  dev.data_ptr() if dev is not None else None, int(dev is not None), self._stream(),
+                  what="adam_step")
+            self._finish(params, shadows)
 
-    def _torch_step(self, group, params, bc1, bc2):
-        b1, b2 = group["betas"]
-        for p in params:
-            st = self.state[p]
-            g = p.grad
-            if group["weight_decay"] != 0:
-                if self.decoupled:
-                    p.mul_(1 - group["lr"] * group["weight_decay"])
-                else:
-                    g = g.add(p, alpha=group["weight_decay"])
-            st["exp_avg"].mul_(b1).add_(g, alpha=1 - b1)
-            st["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1 - b2)
-            v = st["exp_avg_sq"]
-            if group["amsgrad"]:
-                torch.maximum(st["max_exp_avg_sq"], v, out=st["max_exp_avg_sq"])
-                v = st["max_exp_avg_sq"]
-            denom = (v.sqrt() / (bc2 ** 0.5)).add_(group["eps"])
-            p.addcdiv_(st["exp_avg"], denom, value=-group["lr"] / bc1)
+    def _torch_step(self, work):
+        bcs = self._adam_moments("FusedAdam", work, False)
+        for gi, group, params in work:
+            b1, b2 = group["betas"]
+            bc1, bc2 = bcs[gi]
+            for p in params:
+                st = self.state[p]
+                g = p.grad
+                if group["weight_decay"] != 0:
+                    if self.decoupled:
+                        p.mul_(1 - group["lr"] * group["weight_decay"])
+                    else:
+                        g = g.add(p, alpha=group["weight_decay"])
+                st["exp_avg"].mul_(b1).add_(g, alpha=1 - b1)
+                st["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1 - b2)
+                v = st["exp_avg_sq"]
+                if group["amsgrad"]:
+                    torch.maximum(st["max_exp_avg_sq"], v, out=st["max_exp_avg_sq"])
+                    v = st["max_exp_avg_sq"]
+                denom = (v.sqrt() / (bc2 ** 0.5)).add_(group["eps"])
+                p.addcdiv_(st["exp_avg"], denom, value=-group["lr"] / bc1)
 
 
 class FusedAdamW(FusedAdam):
@@ -445,19 +478,10 @@ def _norm_tables(plan, params, adapt):
     return nt
 
 
-def _dense_grads(params):
-    """fp32 gradients laid out like their parameters (what the kernels index)."""
-    grads = [p.grad if p.grad.dtype == torch.float32 else p.grad.float() for p in params]
-    return [g if g.stride() == p.stride() else g.contiguous(memory_format=torch.channels_last
-                                                             if p.dim() == 4 else torch.contiguous_format)
-            for g, p in zip(grads, params)]
-
-
 def multi_tensor_l2norm(tensors):
     """Per-tensor L2 norms (float32 device tensor of ``len(tensors)``) and their global L2 norm
     (0-d device tensor) of fp32 CUDA tensors, contiguous or channels_last-dense: two launches
     for any number of tensors, deterministic (fixed-order sums, no atomics), no host sync."""
-    from ..ops import native_ops
     tensors = list(tensors)
     if not tensors:
         raise ValueError("multi_tensor_l2norm: no tensors")
@@ -467,16 +491,14 @@ def multi_tensor_l2norm(tensors):
                 t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)))):
             raise ValueError("multi_tensor_l2norm: fp32 CUDA tensors on one device, contiguous or "
                              f"channels_last-dense (got {tuple(t.shape)} {t.dtype} {t.device} strides {t.stride()})")
-    lib = native_ops._load()
     plan = _Plan(tensors, dev)
     plan.update({"a": tensors})
     nt = _norm_tables(plan, tensors, [0] * len(tensors))
     glob = torch.zeros(4, dtype=torch.float32, device=dev)
     st = torch.cuda.current_stream().cuda_stream
-    native_ops._chk(lib.pdt_sumsq_chunks(plan.chunks.data_ptr(), plan.nchunks, plan.ptr("a"), None,
-                                         nt.partials.data_ptr(), st), "sumsq_chunks")
-    native_ops._chk(lib.pdt_norm_finalize(nt.partials.data_ptr(), nt.chunk_begin.data_ptr(), nt.n, 1, 0,
-                                          nt.norms.data_ptr(), glob.data_ptr(), 1, 0.0, st), "norm_finalize")
+    _call("sumsq_chunks", plan.chunks.data_ptr(), plan.nchunks, plan.ptr("a"), None, nt.partials.data_ptr(), st)
+    _call("norm_finalize", nt.partials.data_ptr(), nt.chunk_begin.data_ptr(), nt.n, 1, 0, nt.norms.data_ptr(),
+          glob.data_ptr(), 1, 0.0, st)
     return nt.norms[0, :nt.n], glob[2]
 
 
@@ -487,6 +509,7 @@ class _LayerwiseBase(_FusedBase):
 
     The global norm spans every group, so the native path runs only when every group with
     gradients passes ``_native_ok``; otherwise the whole step runs ``_torch_step``."""
+    whole_step_fallback = True
 
     def __init__(self, params, defaults, max_grad_norm, write_bf16_shadow, capturable):
         super().__init__(params, defaults, write_bf16_shadow, capturable)
@@ -509,14 +532,6 @@ class _LayerwiseBase(_FusedBase):
     def _adapt(group, p):
         return not (group["exclude_1d"] and p.dim() <= 1)
 
-    def _work(self):
-        work = []
-        for gi, group in enumerate(self.param_groups):
-            params = [p for p in group["params"] if p.grad is not None]
-            if params:
-                work.append((gi, group, params))
-        return work
-
     def _global(self, device):
         if self._glob is None or self._glob.device != device:
             self._glob = torch.zeros(4, dtype=torch.float32, device=device)
@@ -528,24 +543,13 @@ class _LayerwiseBase(_FusedBase):
         return plan, _norm_tables(plan, params, [self._adapt(group, p) for p in params])
 
     def _sumsq(self, plan, nt, a, b):
-        from ..ops import native_ops
-        native_ops._chk(native_ops._load().pdt_sumsq_chunks(
-            plan.chunks.data_ptr(), plan.nchunks, plan.ptr(a), plan.ptr(b) if b else None,
-            nt.partials.data_ptr(), self._stream()), "sumsq_chunks")
+        _call("sumsq_chunks", plan.chunks.data_ptr(), plan.nchunks, plan.ptr(a), plan.ptr(b) if b else None,
+              nt.partials.data_ptr(), self._stream())
 
     def _finalize(self, nt, nroles, grole, glob, start_zero):
-        from ..ops import native_ops
-        native_ops._chk(native_ops._load().pdt_norm_finalize(
-            nt.partials.data_ptr(), nt.chunk_begin.data_ptr(), nt.n, nroles, grole, nt.norms.data_ptr(),
-            glob.data_ptr() if glob is not None else None, int(start_zero), self.max_grad_norm,
-            self._stream()), "norm_finalize")
-
-    def _finish(self, params, shadows):
-        from ..ops import native_ops
-        _bump_versions(params)
-        if self.write_bf16_shadow:
-            for p, s in zip(params, shadows):
-                native_ops.register_shadow(p, s)
+        _call("norm_finalize", nt.partials.data_ptr(), nt.chunk_begin.data_ptr(), nt.n, nroles, grole,
+              nt.norms.data_ptr(), glob.data_ptr() if glob is not None else None, int(start_zero),
+              self.max_grad_norm, self._stream())
 
     def _torch_clip(self, work):
         """The clip coefficient as a 0-d fp32 tensor (no host sync), or None without clipping."""
@@ -592,21 +596,7 @@ class FusedLARS(_LayerwiseBase):
                         trust_coefficient=trust_coefficient, eps=eps, exclude_1d=exclude_1d)
         super().__init__(params, defaults, max_grad_norm, write_bf16_shadow, capturable)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        self._step_prologue()
-        work = self._work()
-        if not work:
-            return loss
-        if not all(_native_ok(params) for _, _, params in work):
-            self._torch_step(work)
-            return loss
-        from ..ops import native_ops
-        lib = native_ops._load()
+    def _native_step(self, work):
         capturing = torch.cuda.is_current_stream_capturing()
         for _, group, params in work:
             if group["momentum"] == 0:
@@ -623,28 +613,24 @@ class FusedLARS(_LayerwiseBase):
         launches = []
         for k, (gi, group, params) in enumerate(work):
             mom = group["momentum"] != 0
-            none = [None] * len(params)
             shadows = [self._shadow(p) for p in params]
             roles = {"p": params, "g": _dense_grads(params),
-                     "b": [self.state[p]["momentum_buffer"] for p in params] if mom else none,
-                     "s": shadows if self.write_bf16_shadow else none}
+                     "b": [self.state[p]["momentum_buffer"] if mom else None for p in params], "s": shadows}
             plan, nt = self._tables(gi, group, params, roles)
             self._sumsq(plan, nt, "p", "g")
             self._finalize(nt, 2, 1, glob, k == 0)
-            launches.append((gi, group, params, shadows, plan, nt, mom))
+            # (roles: a densified gradient is a temporary that must live until its step is enqueued)
+            launches.append((gi, group, params, shadows, plan, nt, mom, roles))
         # every group's finalize has run: glob holds the norm over all of them
-        for gi, group, params, shadows, plan, nt, mom in launches:
+        for gi, group, params, shadows, plan, nt, mom, _ in launches:
             dev = self._dev_scalars(gi, group, params[0].device) if self.capturable else None
-            rc = lib.pdt_lars_step(
-                plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("g"),
-                plan.ptr("b") if mom else None, plan.ptr("s") if self.write_bf16_shadow else None,
-                nt.flags.data_ptr(), nt.norms.data_ptr(), nt.n, glob.data_ptr(), float(group["lr"]),
-                float(group["momentum"]), float(group["weight_decay"]), int(group["nesterov"]),
-                float(group["trust_coefficient"]), float(group["eps"]),
-                dev.data_ptr() if dev is not None else None, self._stream())
-            native_ops._chk(rc, "lars_step")
+            _call("lars_step", plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("g"),
+                  plan.ptr("b") if mom else None, plan.ptr("s") if self.write_bf16_shadow else None,
+                  nt.flags.data_ptr(), nt.norms.data_ptr(), nt.n, glob.data_ptr(), float(group["lr"]),
+                  float(group["momentum"]), float(group["weight_decay"]), int(group["nesterov"]),
+                  float(group["trust_coefficient"]), float(group["eps"]),
+                  dev.data_ptr() if dev is not None else None, self._stream())
             self._finish(params, shadows)
-        return loss
 
     def _torch_step(self, work):
         clip = self._torch_clip(work)
@@ -690,6 +676,7 @@ class FusedLAMB(_LayerwiseBase):
     count (and the bias corrections for it) advance on the device ahead of stage 1,
     ``state_dict()`` writes the count back into ``step``, and the set of parameters with
     gradients must not change between steps."""
+    dev_width = 4  # [lr, t, bc1, bc2] (bc1 / bc2 are written by the tick kernel)
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, exclude_1d=True,
                  max_grad_norm=0.0, write_bf16_shadow=True, capturable=False):
@@ -697,81 +684,26 @@ class FusedLAMB(_LayerwiseBase):
         super().__init__(params, defaults, max_grad_norm, write_bf16_shadow, capturable)
 
     def state_dict(self):
-        """torch's format; in capturable mode each parameter's ``step`` is first set from the
-        group's device step count (replayed graphs advance only that), as ``FusedAdam`` does."""
-        if self.capturable:
-            for gi, group in enumerate(self.param_groups):
-                d = self._dev.get(gi)
-                if d is None:
-                    continue
-                t = float(d[1].item())
-                for p in group["params"]:
-                    if p in self.state and "step" in self.state[p]:
-                        self.state[p]["step"] = torch.tensor(t)
+        """torch's format (in capturable mode after ``_write_back_steps()``), as ``FusedAdam``'s."""
+        self._write_back_steps()
         return super().state_dict()
 
-    def _dev_scalars(self, gi, group, device, t0=0.0):
-        """The group's device [lr, t, bc1, bc2] (bc1 / bc2 are written by the tick kernel)."""
-        d = self._dev.get(gi)
-        if d is None:
-            d = torch.tensor([float(group["lr"]), float(t0), 1.0, 1.0], dtype=torch.float32, device=device)
-            self._dev[gi] = d
-            self._dev_lr[gi] = float(group["lr"])
-        return d
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        self._step_prologue()
-        work = self._work()
-        if not work:
-            return loss
-        native = all(_native_ok(params) for _, _, params in work)
-        dev_step = self.capturable and native
-        bcs = {}
-        for gi, group, params in work:
-            if dev_step:
-                key = tuple(id(p) for p in params)
-                seen = self._grad_sets.setdefault(gi, key)
-                if seen != key:
-                    raise RuntimeError(
-                        "capturable FusedLAMB: the set of parameters with gradients changed between steps "
-                        f"(group {gi}: {len(seen)} -> {len(key)} params); the group's single device step "
-                        "count requires every parameter to receive a gradient on every step")
-            for p in params:
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = torch.tensor(0.0)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                if not dev_step:  # (capturable: the device count is the step, see state_dict)
-                    st["step"] += 1
-            b1, b2 = group["betas"]
-            step = float(self.state[params[0]]["step"]) if not dev_step else 1.0
-            bcs[gi] = (1 - b1 ** step, 1 - b2 ** step)
-        if not native:
-            self._torch_step(work, bcs)
-            return loss
-        from ..ops import native_ops
-        lib = native_ops._load()
+    def _native_step(self, work):
+        dev_step = self.capturable
+        bcs = self._adam_moments("FusedLAMB", work, dev_step)
         clipping = self.max_grad_norm > 0
         glob = self._global(work[0][2][0].device) if clipping else None
         launches = []
         for k, (gi, group, params) in enumerate(work):
-            none = [None] * len(params)
             shadows = [self._shadow(p) for p in params]
             roles = {"p": params, "g": _dense_grads(params), "m": [self.state[p]["exp_avg"] for p in params],
-                     "v": [self.state[p]["exp_avg_sq"] for p in params],
-                     "s": shadows if self.write_bf16_shadow else none}
+                     "v": [self.state[p]["exp_avg_sq"] for p in params], "s": shadows}
             plan, nt = self._tables(gi, group, params, roles)
             if clipping:
                 self._sumsq(plan, nt, "g", None)
                 self._finalize(nt, 1, 0, glob, k == 0)
-            launches.append((gi, group, params, shadows, plan, nt))
-        for gi, group, params, shadows, plan, nt in launches:
+            launches.append((gi, group, params, shadows, plan, nt, roles))  # (roles: as in FusedLARS)
+        for gi, group, params, shadows, plan, nt, _ in launches:
             b1, b2 = group["betas"]
             bc1, bc2 = bcs[gi]
             dev = self._dev_scalars(gi, group, params[0].device, t0=float(self.state[params[0]]["step"])) \
@@ -779,24 +711,20 @@ class FusedLAMB(_LayerwiseBase):
             devp = dev.data_ptr() if dev is not None else None
             st = self._stream()
             if dev is not None:
-                native_ops._chk(lib.pdt_lamb_tick(devp, float(b1), float(b2), st), "lamb_tick")
-            rc = lib.pdt_lamb_stage1(
-                plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("g"), plan.ptr("m"), plan.ptr("v"),
-                nt.flags.data_ptr(), nt.partials.data_ptr(), glob.data_ptr() if glob is not None else None,
-                float(b1), float(b2), float(1 - b1), float(1 - b2), float(group["eps"]), float(group["weight_decay"]),
-                float(bc1), float(bc2), devp, st)
-            native_ops._chk(rc, "lamb_stage1")
+                _call("lamb_tick", devp, float(b1), float(b2), st)
+            _call("lamb_stage1", plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("g"), plan.ptr("m"),
+                  plan.ptr("v"), nt.flags.data_ptr(), nt.partials.data_ptr(),
+                  glob.data_ptr() if glob is not None else None, float(b1), float(b2), float(1 - b1), float(1 - b2),
+                  float(group["eps"]), float(group["weight_decay"]), float(bc1), float(bc2), devp, st)
             self._finalize(nt, 2, -1, None, False)
-            rc = lib.pdt_lamb_stage2(
-                plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("m"), plan.ptr("v"),
-                plan.ptr("s") if self.write_bf16_shadow else None, nt.flags.data_ptr(), nt.norms.data_ptr(), nt.n,
-                float(group["lr"]), float(group["eps"]), float(group["weight_decay"]), float(bc1), float(bc2),
-                devp, st)
-            native_ops._chk(rc, "lamb_stage2")
+            _call("lamb_stage2", plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("m"), plan.ptr("v"),
+                  plan.ptr("s") if self.write_bf16_shadow else None, nt.flags.data_ptr(), nt.norms.data_ptr(), nt.n,
+                  float(group["lr"]), float(group["eps"]), float(group["weight_decay"]), float(bc1), float(bc2),
+                  devp, st)
             self._finish(params, shadows)
-        return loss
 
-    def _torch_step(self, work, bcs):
+    def _torch_step(self, work):
+        bcs = self._adam_moments("FusedLAMB", work, False)
         clip = self._torch_clip(work)
         for gi, group, params in work:
             b1, b2 = group["betas"]
