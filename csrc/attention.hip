@@ -19,7 +19,6 @@
 // over all query tiles) and a dQ kernel (one workgroup per 64 queries) -- the
 // probabilities are recomputed from Q, K and the saved log-sum-exp, no atomics.
 #include "pdt_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -835,33 +834,10 @@ static int seq_nkt(int T) {
   return n <= 16 ? n : 0;
 }
 
-#define PDT_SEQ_SWITCH(N, CALL) \
-  switch (N) {                  \
-    case 1: CALL(1); break;     \
-    case 2: CALL(2); break;     \
-    case 3: CALL(3); break;     \
-    case 4: CALL(4); break;     \
-    case 5: CALL(5); break;     \
-    case 6: CALL(6); break;     \
-    case 7: CALL(7); break;     \
-    case 8: CALL(8); break;     \
-    case 9: CALL(9); break;     \
-    case 10: CALL(10); break;   \
-    case 11: CALL(11); break;   \
-    case 12: CALL(12); break;   \
-    case 13: CALL(13); break;   \
-    case 14: CALL(14); break;   \
-    case 15: CALL(15); break;   \
-    default: CALL(16); break;   \
-  }
-
 // PDT_ATTN_BWD_SINGLE=0: the two-image (row + transposed) backward staging, for A/B runs
 static int g_attn_bwd_single = -1;
 static int attn_bwd_single() {
-  if (g_attn_bwd_single < 0) {
-    const char* e = getenv("PDT_ATTN_BWD_SINGLE");
-    g_attn_bwd_single = (e && e[0] == '0') ? 0 : 1;
-  }
+  if (g_attn_bwd_single < 0) g_attn_bwd_single = pdt_env_flag("PDT_ATTN_BWD_SINGLE", 1);
   return g_attn_bwd_single;
 }
 PDT_API int pdt_attn_set_bwd_single(int on) {
@@ -873,10 +849,7 @@ PDT_API int pdt_attn_set_bwd_single(int on) {
 // the whole-sequence ones apply (T <= 256)
 static int g_attn_tiled = -1;
 static int attn_seq_disabled() {
-  if (g_attn_tiled < 0) {
-    const char* e = getenv("PDT_ATTN_TILED");
-    g_attn_tiled = (e && e[0] == '1') ? 1 : 0;
-  }
+  if (g_attn_tiled < 0) g_attn_tiled = pdt_env_flag("PDT_ATTN_TILED", 0);
   return g_attn_tiled;
 }
 PDT_API int pdt_attn_set_tiled(int on) {
@@ -886,19 +859,15 @@ PDT_API int pdt_attn_set_tiled(int on) {
 
 PDT_API int pdt_attn_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, float scale, hipStream_t st) {
   AttnParams p;
-  p.qkv = (const u16*)qkv;
+  pdt_attn_fill(p, qkv, B, T, H, scale);
   p.out = (u16*)out;
   p.lse = lse;
-  p.B = B; p.T = T; p.H = H;
-  p.ld = 3L * H * D;
-  p.ldo = (long)H * D;
-  p.c = scale * 1.4426950408889634f;
   const int nkt = attn_seq_disabled() ? 0 : seq_nkt(T);
   if (nkt) {
     dim3 g(B * H);
-#define FWD_SEQ(N) hipLaunchKernelGGL(attn_fwd_seq_kernel<N>, g, dim3(256), 0, st, p)
-    PDT_SEQ_SWITCH(nkt, FWD_SEQ)
-#undef FWD_SEQ
+    pdt_dispatch<1, 16>(nkt, [&](auto n) {
+      hipLaunchKernelGGL(attn_fwd_seq_kernel<decltype(n)::value>, g, dim3(256), 0, st, p);
+    });
     PDT_RETURN_LAUNCH();
   }
   dim3 grid((T + TILE - 1) / TILE, B * H);
@@ -908,7 +877,54 @@ PDT_API int pdt_attn_fwd(const void* qkv, void* out, float* lse, int B, int T, i
 
 static int attn_bwd_impl(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                          void* dqkv, int B, int T, int H, float scale, void* q8, float* q8_meta, float* q8_part,
-                         float* q8_dq, hipStream_t st);
+                         float* q8_dq, hipStream_t st) {
+  const int nkt = attn_seq_disabled() ? 0 : seq_nkt(T);
+  if (nkt) {
+    AttnSeqBwdParams q;
+    pdt_attn_fill(q, qkv, B, T, H, scale);
+    q.q8 = (uint8_t*)q8;
+    q.q8_meta = q8_meta;
+    q.q8_part = q8_part;
+    q.out = (const u16*)out;
+    q.dout = (const u16*)dout;
+    q.lse = lse;
+    q.dqkv = (u16*)dqkv;
+    q.scale = scale;
+    dim3 g(B * H);
+    pdt_dispatch<1, 16>(nkt, [&](auto n) {
+      constexpr int N = decltype(n)::value;
+      if (attn_bwd_single()) {
+        hipLaunchKernelGGL((attn_bwd_dkdv_seq_kernel<N, true>), g, dim3(512), 0, st, q);
+        hipLaunchKernelGGL((attn_bwd_dq_seq_kernel<N, true>), g, dim3(512), 0, st, q);
+      } else {
+        hipLaunchKernelGGL((attn_bwd_dkdv_seq_kernel<N, false>), g, dim3(512), 0, st, q);
+        hipLaunchKernelGGL((attn_bwd_dq_seq_kernel<N, false>), g, dim3(512), 0, st, q);
+      }
+    });
+    if (q8 == nullptr) PDT_RETURN_LAUNCH();
+    const int e = (int)hipGetLastError();
+    if (e) return e;
+    return pdt_fp8_meta_roll_partial(q8_meta, q8_part, 2 * B * H, 1, q8_dq, st);
+  }
+  const long rows = (long)B * T * H;
+  hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, st, (const u16*)dout,
+                     (const u16*)out, delta, B, T, H, (long)H * D);
+  int e = (int)hipGetLastError();
+  if (e) return e;
+  AttnBwdParams p;
+  pdt_attn_fill(p, qkv, B, T, H, scale);
+  p.dout = (const u16*)dout;
+  p.lse = lse;
+  p.delta = delta;
+  p.dqkv = (u16*)dqkv;
+  p.scale = scale;
+  dim3 grid((T + TILE - 1) / TILE, B * H);
+  hipLaunchKernelGGL(attn_bwd_dkdv_kernel, grid, dim3(256), 0, st, p);
+  e = (int)hipGetLastError();
+  if (e) return e;
+  hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, dim3(256), 0, st, p);
+  PDT_RETURN_LAUNCH();
+}
 
 PDT_API int pdt_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                          void* dqkv, int B, int T, int H, float scale, hipStream_t st) {
@@ -923,63 +939,4 @@ PDT_API int pdt_attn_bwd_q8(const void* qkv, const void* out, const void* dout, 
                             float* q8_dq, hipStream_t st) {
   if (!q8 || !q8_meta || !q8_part || attn_seq_disabled() || !seq_nkt(T)) return -1;
   return attn_bwd_impl(qkv, out, dout, lse, delta, dqkv, B, T, H, scale, q8, q8_meta, q8_part, q8_dq, st);
-}
-
-static int attn_bwd_impl(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
-                         void* dqkv, int B, int T, int H, float scale, void* q8, float* q8_meta, float* q8_part,
-                         float* q8_dq, hipStream_t st) {
-  const int nkt = attn_seq_disabled() ? 0 : seq_nkt(T);
-  if (nkt) {
-    AttnSeqBwdParams q;
-    q.q8 = (uint8_t*)q8;
-    q.q8_meta = q8_meta;
-    q.q8_part = q8_part;
-    q.qkv = (const u16*)qkv;
-    q.out = (const u16*)out;
-    q.dout = (const u16*)dout;
-    q.lse = lse;
-    q.dqkv = (u16*)dqkv;
-    q.B = B; q.T = T; q.H = H;
-    q.ld = 3L * H * D;
-    q.ldo = (long)H * D;
-    q.c = scale * 1.4426950408889634f;
-    q.scale = scale;
-    dim3 g(B * H);
-#define SEQ_BWD(N)                                                                     \
-  if (attn_bwd_single()) {                                                             \
-    hipLaunchKernelGGL((attn_bwd_dkdv_seq_kernel<N, true>), g, dim3(512), 0, st, q);   \
-    hipLaunchKernelGGL((attn_bwd_dq_seq_kernel<N, true>), g, dim3(512), 0, st, q);     \
-  } else {                                                                             \
-    hipLaunchKernelGGL((attn_bwd_dkdv_seq_kernel<N, false>), g, dim3(512), 0, st, q);  \
-    hipLaunchKernelGGL((attn_bwd_dq_seq_kernel<N, false>), g, dim3(512), 0, st, q);    \
-  }
-    PDT_SEQ_SWITCH(nkt, SEQ_BWD)
-#undef SEQ_BWD
-    if (q8 == nullptr) PDT_RETURN_LAUNCH();
-    const int e = (int)hipGetLastError();
-    if (e) return e;
-    return pdt_fp8_meta_roll_partial(q8_meta, q8_part, 2 * B * H, 1, q8_dq, st);
-  }
-  const long rows = (long)B * T * H;
-  hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, st, (const u16*)dout,
-                     (const u16*)out, delta, B, T, H, (long)H * D);
-  int e = (int)hipGetLastError();
-  if (e) return e;
-  AttnBwdParams p;
-  p.qkv = (const u16*)qkv;
-  p.dout = (const u16*)dout;
-  p.lse = lse;
-  p.delta = delta;
-  p.dqkv = (u16*)dqkv;
-  p.B = B; p.T = T; p.H = H;
-  p.ld = 3L * H * D;
-  p.ldo = (long)H * D;
-  p.c = scale * 1.4426950408889634f;
-  p.scale = scale;
-  dim3 grid((T + TILE - 1) / TILE, B * H);
-  hipLaunchKernelGGL(attn_bwd_dkdv_kernel, grid, dim3(256), 0, st, p);
-  e = (int)hipGetLastError();
-  if (e) return e;
-  hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, dim3(256), 0, st, p);
-  PDT_RETURN_LAUNCH();
 }

@@ -29,7 +29,6 @@
 // bf16 kernels do. lse is the forward's (log2 domain), delta = rowsum(dO * O) is computed
 // here from the bf16 O and dO.
 #include "fp8_mfma.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -447,14 +446,39 @@ __global__ void __launch_bounds__(512) attn_bwd_f8_kernel(AttnBwdF8Params p) {
 
 }  // namespace
 
-// fused fp8 backward for T <= 256, head dim 64 (d(qkv) bf16); -1 when not covered
-static int attn_bwd_f8(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B,
-                       int T, int H, float scale, float* dbg, const AttnBwdF8Params* q8, hipStream_t st);
-
 // Workgroups of the backward launch: the length of the q8_part the caller passes to
 // pdt_attn_bwd_f8_q8.
-static int attn_bwd_grid(int nbh);
+// PDT_ATTN_BWD_PERSIST=0: one workgroup per head (the grid B*H, each running the head loop
+// once) instead of one per CU -- an A/B switch
+static int attn_bwd_grid(int nbh) {
+  static const int persist = pdt_env_flag("PDT_ATTN_BWD_PERSIST", 1);
+  const int g = persist ? pdt_num_cus() : nbh;
+  return nbh < g ? nbh : g;
+}
 PDT_API int pdt_attn_bwd_f8_grid(int B, int H) { return attn_bwd_grid(B * H); }
+
+// fused fp8 backward for T <= 256, head dim 64 (d(qkv) bf16); -1 when not covered
+static int attn_bwd_f8(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B,
+                       int T, int H, float scale, float* dbg, const AttnBwdF8Params* q8, hipStream_t st) {
+  if (T < 1 || T > 256) return -1;
+  AttnBwdF8Params p = q8 ? *q8 : AttnBwdF8Params{};
+  pdt_attn_fill(p, qkv, B, T, H, scale);
+  p.out = (const u16*)out;
+  p.dout = (const u16*)dout;
+  p.lse = lse;
+  p.dqkv = (u16*)dqkv;
+  p.scale = scale;
+  p.dbg = dbg;
+  // one workgroup per CU (the LDS images hold 137 KB), each walking B*H / grid heads
+  dim3 g(attn_bwd_grid(B * H));
+  pdt_dispatch<1, 4>((T + 63) / 64, [&](auto n) {
+    constexpr int NQP = decltype(n)::value;
+    if (dbg != nullptr) hipLaunchKernelGGL((attn_bwd_f8_kernel<NQP, true>), g, dim3(512), 0, st, p);
+    else if (q8 != nullptr) hipLaunchKernelGGL((attn_bwd_f8_kernel<NQP, false, true>), g, dim3(512), 0, st, p);
+    else hipLaunchKernelGGL((attn_bwd_f8_kernel<NQP>), g, dim3(512), 0, st, p);
+  });
+  PDT_RETURN_LAUNCH();
+}
 
 // pdt_attn_bwd_f8 with the qkv projection's gradient epilogue (Q8 above): the e5m2 codes of
 // d(qkv) with the delayed scale q8_meta[0] -> q8 ([B*T][3*H*64]), the amax history rolled
@@ -490,48 +514,4 @@ PDT_API int pdt_attn_bwd_f8(const void* qkv, const void* out, const void* dout, 
 PDT_API int pdt_attn_bwd_f8_debug(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                                   int B, int T, int H, float scale, float* dbg, hipStream_t st) {
   return attn_bwd_f8(qkv, out, dout, lse, dqkv, B, T, H, scale, dbg, nullptr, st);
-}
-
-// PDT_ATTN_BWD_PERSIST=0: one workgroup per head (the grid B*H, each running the head loop
-// once) instead of one per CU -- an A/B switch
-static int attn_bwd_grid(int nbh) {
-  static int persist = -1;
-  if (persist < 0) {
-    const char* e = getenv("PDT_ATTN_BWD_PERSIST");
-    persist = (e && e[0] == '0') ? 0 : 1;
-  }
-  const int g = persist ? pdt_num_cus() : nbh;
-  return nbh < g ? nbh : g;
-}
-
-static int attn_bwd_f8(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B,
-                       int T, int H, float scale, float* dbg, const AttnBwdF8Params* q8, hipStream_t st) {
-  if (T < 1 || T > 256) return -1;
-  AttnBwdF8Params p = q8 ? *q8 : AttnBwdF8Params{};
-  p.qkv = (const u16*)qkv;
-  p.out = (const u16*)out;
-  p.dout = (const u16*)dout;
-  p.lse = lse;
-  p.dqkv = (u16*)dqkv;
-  p.B = B; p.T = T; p.H = H;
-  p.ld = 3L * H * D;
-  p.ldo = (long)H * D;
-  p.c = scale * 1.4426950408889634f;
-  p.scale = scale;
-  p.dbg = dbg;
-  const int nqp = (T + 63) / 64;
-  // one workgroup per CU (the LDS images hold 137 KB), each walking B*H / grid heads
-  dim3 g(attn_bwd_grid(B * H));
-#define BWD(N)                                                                                  \
-  if (dbg != nullptr) hipLaunchKernelGGL((attn_bwd_f8_kernel<N, true>), g, dim3(512), 0, st, p);            \
-  else if (q8 != nullptr) hipLaunchKernelGGL((attn_bwd_f8_kernel<N, false, true>), g, dim3(512), 0, st, p); \
-  else hipLaunchKernelGGL((attn_bwd_f8_kernel<N>), g, dim3(512), 0, st, p)
-  switch (nqp) {
-    case 1: BWD(1); break;
-    case 2: BWD(2); break;
-    case 3: BWD(3); break;
-    default: BWD(4); break;
-  }
-#undef BWD
-  PDT_RETURN_LAUNCH();
 }

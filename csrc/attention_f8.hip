@@ -442,20 +442,13 @@ __global__ void __launch_bounds__(64 * NW) attn_fwd_f8_kernel(AttnF8Params p) {
 // rate saves) and it adds ~1.5 % logits error (profiles/vit_b16_fp8_bs1024_step_round3_*).
 static int g_attn_pv8 = -1;
 static int attn_pv8() {
-  if (g_attn_pv8 < 0) {
-    const char* e = getenv("PDT_FP8_ATTN_PV");
-    g_attn_pv8 = (e && e[0] == '1') ? 1 : 0;
-  }
+  if (g_attn_pv8 < 0) g_attn_pv8 = pdt_env_flag("PDT_FP8_ATTN_PV", 0);
   return g_attn_pv8;
 }
 // PDT_ATTN_FWD_NW8=0: the 4-wave forward for T > 128 as well (A/B switch; 8 waves give each of
 // the 7 query tiles of T = 197 its own wave instead of 2 rounds with one wave idle)
 static int attn_fwd_nw8() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("PDT_ATTN_FWD_NW8");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
+  static const int v = pdt_env_flag("PDT_ATTN_FWD_NW8", 1);
   return v;
 }
 
@@ -464,45 +457,48 @@ PDT_API int pdt_attn_set_pv8(int on) {
   return 0;
 }
 
+// parameters of a T <= 256 forward; the codes' three pointers are null without q8
+static AttnF8Params attn_f8_params(const void* qkv, void* out, float* lse, int B, int T, int H, float scale, void* q8,
+                                   const float* q8_meta, float* q8_part) {
+  AttnF8Params p;
+  pdt_attn_fill(p, qkv, B, T, H, scale);
+  p.out = (u16*)out;
+  p.lse = lse;
+  p.q8 = (uint8_t*)q8; p.q8_meta = q8_meta; p.q8_part = q8_part;
+  return p;
+}
+
+// attn_fwd_f8_kernel<ceil(T / 32), f8, ...>, one workgroup per (batch, head). fp8 scores with
+// T > 128 take 8 waves, one 32-query tile each (T = 197: 7), with the output codes compiled in
+// or out (q8); everything else 4 waves, the codes decided by p.q8 at run time.
+static int attn_fwd_launch(const AttnF8Params& p, bool f8, bool q8, hipStream_t st) {
+  const int nkt = (p.T + 31) / 32;
+  dim3 g(p.B * p.H);
+  if (!f8) {
+    pdt_dispatch<1, 8>(nkt, [&](auto n) {
+      hipLaunchKernelGGL((attn_fwd_f8_kernel<decltype(n)::value, false>), g, dim3(256), 0, st, p);
+    });
+  } else if (nkt >= 5 && !attn_pv8() && attn_fwd_nw8()) {
+    pdt_dispatch<5, 8>(nkt, [&](auto n) {
+      constexpr int N = decltype(n)::value;
+      if (q8) hipLaunchKernelGGL((attn_fwd_f8_kernel<N, true, false, 8, 1>), g, dim3(512), 0, st, p);
+      else hipLaunchKernelGGL((attn_fwd_f8_kernel<N, true, false, 8, 0>), g, dim3(512), 0, st, p);
+    });
+  } else {
+    pdt_dispatch<1, 8>(nkt, [&](auto n) {
+      constexpr int N = decltype(n)::value;
+      if (attn_pv8()) hipLaunchKernelGGL((attn_fwd_f8_kernel<N, true, true>), g, dim3(256), 0, st, p);
+      else hipLaunchKernelGGL((attn_fwd_f8_kernel<N, true, false>), g, dim3(256), 0, st, p);
+    });
+  }
+  PDT_RETURN_LAUNCH();
+}
+
 // fp8 forward for T <= 256, head dim 64; -1 when the geometry is not covered
 PDT_API int pdt_attn_fwd_f8(const void* qkv, void* out, float* lse, int B, int T, int H, float scale,
                             hipStream_t st) {
   if (T < 1 || T > 256) return -1;
-  AttnF8Params p;
-  p.qkv = (const u16*)qkv;
-  p.out = (u16*)out;
-  p.lse = lse;
-  p.B = B; p.T = T; p.H = H;
-  p.ld = 3L * H * D;
-  p.ldo = (long)H * D;
-  p.c = scale * 1.4426950408889634f;
-  p.q8 = nullptr; p.q8_meta = nullptr; p.q8_part = nullptr;
-  const int nkt = (T + 31) / 32;
-  dim3 g(B * H);
-  if (nkt >= 5 && !attn_pv8() && attn_fwd_nw8()) {  // 8 waves: one 32-query tile each (T = 197: 7)
-    switch (nkt) {
-      case 5: hipLaunchKernelGGL((attn_fwd_f8_kernel<5, true, false, 8, 0>), g, dim3(512), 0, st, p); break;
-      case 6: hipLaunchKernelGGL((attn_fwd_f8_kernel<6, true, false, 8, 0>), g, dim3(512), 0, st, p); break;
-      case 7: hipLaunchKernelGGL((attn_fwd_f8_kernel<7, true, false, 8, 0>), g, dim3(512), 0, st, p); break;
-      default: hipLaunchKernelGGL((attn_fwd_f8_kernel<8, true, false, 8, 0>), g, dim3(512), 0, st, p); break;
-    }
-    PDT_RETURN_LAUNCH();
-  }
-#define F8(N)                                                                         \
-  if (attn_pv8()) hipLaunchKernelGGL((attn_fwd_f8_kernel<N, true, true>), g, dim3(256), 0, st, p); \
-  else hipLaunchKernelGGL((attn_fwd_f8_kernel<N, true, false>), g, dim3(256), 0, st, p)
-  switch (nkt) {
-    case 1: F8(1); break;
-    case 2: F8(2); break;
-    case 3: F8(3); break;
-    case 4: F8(4); break;
-    case 5: F8(5); break;
-    case 6: F8(6); break;
-    case 7: F8(7); break;
-    default: F8(8); break;
-  }
-#undef F8
-  PDT_RETURN_LAUNCH();
+  return attn_fwd_launch(attn_f8_params(qkv, out, lse, B, T, H, scale, nullptr, nullptr, nullptr), true, false, st);
 }
 
 // pdt_attn_fwd_f8 that also writes the e4m3 codes of O for the projection GEMM (delayed scale
@@ -511,41 +507,7 @@ PDT_API int pdt_attn_fwd_f8(const void* qkv, void* out, float* lse, int B, int T
 PDT_API int pdt_attn_fwd_f8_q8(const void* qkv, void* out, float* lse, int B, int T, int H, float scale, void* q8,
                                float* q8_meta, float* q8_part, float* q8_dq, hipStream_t st) {
   if (T < 1 || T > 256 || !q8 || !q8_meta || !q8_part) return -1;
-  AttnF8Params p;
-  p.qkv = (const u16*)qkv;
-  p.out = (u16*)out;
-  p.lse = lse;
-  p.B = B; p.T = T; p.H = H;
-  p.ld = 3L * H * D;
-  p.ldo = (long)H * D;
-  p.c = scale * 1.4426950408889634f;
-  p.q8 = (uint8_t*)q8; p.q8_meta = q8_meta; p.q8_part = q8_part;
-  const int nkt = (T + 31) / 32;
-  dim3 g(B * H);
-  if (nkt >= 5 && !attn_pv8() && attn_fwd_nw8()) {  // 8 waves, as in pdt_attn_fwd_f8
-    switch (nkt) {
-      case 5: hipLaunchKernelGGL((attn_fwd_f8_kernel<5, true, false, 8, 1>), g, dim3(512), 0, st, p); break;
-      case 6: hipLaunchKernelGGL((attn_fwd_f8_kernel<6, true, false, 8, 1>), g, dim3(512), 0, st, p); break;
-      case 7: hipLaunchKernelGGL((attn_fwd_f8_kernel<7, true, false, 8, 1>), g, dim3(512), 0, st, p); break;
-      default: hipLaunchKernelGGL((attn_fwd_f8_kernel<8, true, false, 8, 1>), g, dim3(512), 0, st, p); break;
-    }
-  } else {
-#define F8(N)                                                                         \
-  if (attn_pv8()) hipLaunchKernelGGL((attn_fwd_f8_kernel<N, true, true>), g, dim3(256), 0, st, p); \
-  else hipLaunchKernelGGL((attn_fwd_f8_kernel<N, true, false>), g, dim3(256), 0, st, p)
-    switch (nkt) {
-      case 1: F8(1); break;
-      case 2: F8(2); break;
-      case 3: F8(3); break;
-      case 4: F8(4); break;
-      case 5: F8(5); break;
-      case 6: F8(6); break;
-      case 7: F8(7); break;
-      default: F8(8); break;
-    }
-#undef F8
-  }
-  int e = (int)hipGetLastError();
+  const int e = attn_fwd_launch(attn_f8_params(qkv, out, lse, B, T, H, scale, q8, q8_meta, q8_part), true, true, st);
   if (e) return e;
   return pdt_fp8_meta_roll_partial(q8_meta, q8_part, B * H, 0, q8_dq, st);
 }
@@ -554,28 +516,5 @@ PDT_API int pdt_attn_fwd_f8_q8(const void* qkv, void* out, float* lse, int B, in
 PDT_API int pdt_attn_fwd_tiles(const void* qkv, void* out, float* lse, int B, int T, int H, float scale,
                                hipStream_t st) {
   if (T < 1 || T > 256) return -1;
-  AttnF8Params p;
-  p.qkv = (const u16*)qkv;
-  p.out = (u16*)out;
-  p.lse = lse;
-  p.B = B; p.T = T; p.H = H;
-  p.ld = 3L * H * D;
-  p.ldo = (long)H * D;
-  p.c = scale * 1.4426950408889634f;
-  p.q8 = nullptr; p.q8_meta = nullptr; p.q8_part = nullptr;
-  const int nkt = (T + 31) / 32;
-  dim3 g(B * H);
-#define BF(N) hipLaunchKernelGGL((attn_fwd_f8_kernel<N, false>), g, dim3(256), 0, st, p)
-  switch (nkt) {
-    case 1: BF(1); break;
-    case 2: BF(2); break;
-    case 3: BF(3); break;
-    case 4: BF(4); break;
-    case 5: BF(5); break;
-    case 6: BF(6); break;
-    case 7: BF(7); break;
-    default: BF(8); break;
-  }
-#undef BF
-  PDT_RETURN_LAUNCH();
+  return attn_fwd_launch(attn_f8_params(qkv, out, lse, B, T, H, scale, nullptr, nullptr, nullptr), false, false, st);
 }

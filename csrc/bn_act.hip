@@ -468,14 +468,12 @@ __global__ void __launch_bounds__(NT) bn_bwd_apply_kernel(const u16* __restrict_
 // (scripts/bench_bn.py, one MI355X): apply 4.49 / 4.38 / 4.45 TB/s and backward apply
 // 4.91 / 4.47 / 4.44 TB/s for U = 1 / 2 / 4 -- the grid-stride loop already keeps
 // enough bytes in flight; deeper trips only cost occupancy.
-int g_bn_unroll = -1;
 int bn_unroll() {
-  if (g_bn_unroll < 0) {
-    const char* e = getenv("PDT_BN_UNROLL");
-    int u = e ? atoi(e) : 1;
-    g_bn_unroll = (u == 1 || u == 2 || u == 4 || u == 11) ? u : 1;
-  }
-  return g_bn_unroll;
+  static const int unroll = [] {
+    const int u = pdt_env_int("PDT_BN_UNROLL", 1);
+    return (u == 1 || u == 2 || u == 4 || u == 11) ? u : 1;
+  }();
+  return unroll;
 }
 
 int gcd_i(int a, int b) { return b ? gcd_i(b, a % b) : a; }
@@ -502,12 +500,10 @@ PDT_API int pdt_bn_stats_blocks(long M, int C) {
   int rp = NT / cpr;
   long b = (M + rp - 1) / rp;
   // several blocks per CU, each streaming many rows (PDT_BN_BLOCKS overrides the cap)
-  static int cap = -1;
-  if (cap < 0) {
-    const char* e = getenv("PDT_BN_BLOCKS");
-    cap = e ? atoi(e) : 512;
-    if (cap < 1) cap = 512;
-  }
+  static const int cap = [] {
+    const int v = pdt_env_int("PDT_BN_BLOCKS", 512);
+    return v < 1 ? 512 : v;
+  }();
   if (b > cap) b = cap;
   if (b < 1) b = 1;
   return (int)b;

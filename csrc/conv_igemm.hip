@@ -389,14 +389,8 @@ static int conv_nt_impl(const void* src, const void* b, void* out, float* stats,
   p.div_Cs8 = make_fastdiv(Cs / 8);
   p.div_ntw = make_fastdiv(ntw > 0 ? ntw : 1);
   p.ident_out = (Hm == Ho && Wm == Wo && osh == 1 && osw == 1 && oph == 0 && opw == 0) ? 1 : 0;
-  {
-    static int nt_env = -1;
-    if (nt_env < 0) {
-      const char* e = getenv("PDT_NT_STORE");
-      nt_env = (e && e[0] == '1') ? 1 : 0;
-    }
-    p.nt_store = nt_env;
-  }
+  static const int nt_env = pdt_env_flag("PDT_NT_STORE", 0);
+  p.nt_store = nt_env;
   const int v = pdt_conv_nt_resolve_variant(variant, p.M, Ncol, K);
   p.nstat_rows = pdt_conv_nt_stat_rows(p.M, Ncol, K, v);
   if (ax.mode != 0) {

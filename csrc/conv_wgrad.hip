@@ -588,11 +588,8 @@ static int wgrad_plan(int M, int Mo, int No, int variant, int* ktiles_per_split)
   int smax = (target + tiles - 1) / tiles;
   if (smax > nk) smax = nk;
   if (smax < 1) smax = 1;
-  static int mode = -1;  // PDT_WG_PLAN: 0 legacy for every tile, 1 wave plan for every tile, unset: by tile
-  if (mode < 0) {
-    const char* e = getenv("PDT_WG_PLAN");
-    mode = (e && e[0] == '0') ? 0 : (e && e[0] == '1') ? 1 : 2;
-  }
+  // PDT_WG_PLAN: 0 legacy for every tile, 1 wave plan for every tile, unset (or anything else): by tile
+  static const int mode = !pdt_env_flag("PDT_WG_PLAN", 1) ? 0 : pdt_env_flag("PDT_WG_PLAN", 0) ? 1 : 2;
   int splits = smax;
   // the wave model fits one-workgroup-per-CU tiles (every resident workgroup runs at the same
   // rate): those take it by default; multi-workgroup tiles only with PDT_WG_PLAN=1
@@ -691,14 +688,8 @@ PDT_API int pdt_conv_wgrad2(const void* dy, const void* x, float* slab, float* o
   const int G = reduce_groups(splits, Mo, No);
   // bias_out (optional, fp32 [Mo]): also the column sums of dY, from the same pass
   p.bslab = bias_out ? slab + (long)splits * Mo * No + (G > 1 ? (long)G * Mo * No : 0) : nullptr;
-  {
-    static int xcd_env = -1;
-    if (xcd_env < 0) {
-      const char* e = getenv("PDT_WGRAD_XCD");
-      xcd_env = (e && e[0] == '0') ? 0 : 1;
-    }
-    p.xcd = xcd_env;
-  }
+  static const int xcd_env = pdt_env_flag("PDT_WGRAD_XCD", 1);
+  p.xcd = xcd_env;
   p.div_Wm = make_fastdiv(Wm);
   p.div_HWm = make_fastdiv(Hm * Wm);
   p.div_C = make_fastdiv(C);

@@ -484,11 +484,7 @@ PDT_API int pdt_gelu_dual_cast_fp8(const void* y, long n, float* meta, int fmt, 
 // block shape of the column-summing casts: one thread per 8-column chunk, times up to 8 row groups
 // (PDT_CAST_CS_RG=1: the previous one-row-walker-per-chunk shape, for A/B runs)
 static void cs_block(int cols, int* nt, int* rg) {
-  static int env = -1;
-  if (env < 0) {
-    const char* e = getenv("PDT_CAST_CS_RG");
-    env = e ? atoi(e) : 0;
-  }
+  static const int env = pdt_env_int("PDT_CAST_CS_RG", 0);
   const int c8n = cols / 8;
   int g = c8n <= 1024 ? 1024 / c8n : 1;
   if (g > 8) g = 8;
@@ -537,11 +533,7 @@ static int cs_blocks_per_cu(const void* kern, int nt, size_t sh) {
 static size_t cs_lds_bytes(int cols, int rg) { return rg > 1 ? (size_t)rg * (cols / 8) * 2 * sizeof(f32x4) : 0; }
 
 static int cs_launch_bands(const void* kern, int rows, int nt, size_t sh) {
-  static int env = -1;
-  if (env < 0) {
-    const char* e = getenv("PDT_CAST_CS_ROUNDS");
-    env = e ? atoi(e) : 1;
-  }
+  static const int env = pdt_env_int("PDT_CAST_CS_ROUNDS", 1);
   const int nb = pdt_cast_cs_bands(rows);
   if (env == 0) return nb;
   const int per = cs_blocks_per_cu(kern, nt, sh);
@@ -604,8 +596,7 @@ PDT_API int pdt_cast_fp8_gelu_grad_cs(const void* x, const void* z, int rows, in
 // forward (a 256-thread block walked them in ~24 us); PDT_ROLL_NT overrides (256 / 512 / 1024)
 static int roll_threads(int nblk) {
   static const int nt = [] {
-    const char* e = getenv("PDT_ROLL_NT");
-    const int v = e ? atoi(e) : 1024;
+    const int v = pdt_env_int("PDT_ROLL_NT", 1024);
     return (v == 256 || v == 512) ? v : 1024;
   }();
   return nblk <= 1024 ? 256 : nt;

@@ -358,17 +358,28 @@ __global__ void gelu_bwd_kernel(const u16* __restrict__ dy, const u16* __restric
 
 }  // namespace
 
+// chunks of 4 per lane of the instantiation for width D (D = 256, 512, 768, 1024); 0: not covered
+static int ln_chunks(int D) { return (D % 256 == 0 && D >= 256 && D <= 1024) ? D / 256 : 0; }
+
+// ln_fwd_kernel<D / 256, f8>, one wave per row; -1 with nothing launched when D is not covered
+static int ln_fwd_launch(bool f8, const void* x, const float* g, const float* b, void* y, float* mean, float* rstd,
+                         int rows, int D, float eps, void* q, const float* meta, float* amax_part, const void* r,
+                         void* xsum, hipStream_t st) {
+  const int ch = ln_chunks(D);
+  if (!ch) return -1;
+  dim3 grid((rows + WPB - 1) / WPB), blk(64 * WPB);
+  pdt_dispatch<1, 4>(ch, [&](auto n) {
+    constexpr int CH = decltype(n)::value;
+    auto kern = f8 ? ln_fwd_kernel<CH, true> : ln_fwd_kernel<CH, false>;
+    hipLaunchKernelGGL(kern, grid, blk, 0, st, (const u16*)x, g, b, (u16*)y, mean, rstd, rows, eps, (uint8_t*)q, meta,
+                       amax_part, (const u16*)r, (u16*)xsum);
+  });
+  return (int)hipGetLastError();
+}
+
 PDT_API int pdt_ln_fwd(const void* x, const float* g, const float* b, void* y, float* mean, float* rstd, int rows,
                        int D, float eps, hipStream_t st) {
-  dim3 grid((rows + WPB - 1) / WPB), blk(64 * WPB);
-  switch (D) {
-    case 256: hipLaunchKernelGGL(ln_fwd_kernel<1>, grid, blk, 0, st, (const u16*)x, g, b, (u16*)y, mean, rstd, rows, eps); break;
-    case 512: hipLaunchKernelGGL(ln_fwd_kernel<2>, grid, blk, 0, st, (const u16*)x, g, b, (u16*)y, mean, rstd, rows, eps); break;
-    case 768: hipLaunchKernelGGL(ln_fwd_kernel<3>, grid, blk, 0, st, (const u16*)x, g, b, (u16*)y, mean, rstd, rows, eps); break;
-    case 1024: hipLaunchKernelGGL(ln_fwd_kernel<4>, grid, blk, 0, st, (const u16*)x, g, b, (u16*)y, mean, rstd, rows, eps); break;
-    default: return -1;
-  }
-  PDT_RETURN_LAUNCH();
+  return ln_fwd_launch(false, x, g, b, y, mean, rstd, rows, D, eps, nullptr, nullptr, nullptr, nullptr, nullptr, st);
 }
 
 PDT_API int pdt_ln_fwd_f8_blocks(int rows) { return (rows + WPB - 1) / WPB; }
@@ -381,32 +392,9 @@ PDT_API int pdt_ln_add_fwd(const void* x, const void* r, void* xsum, const float
                            float* mean, float* rstd, int rows, int D, float eps, void* q, float* meta,
                            float* amax_part, float* dq_out, hipStream_t st) {
   if (!r || !xsum || (q && (!meta || !amax_part)) || (!q && !y)) return -1;
-  const int nb = (rows + WPB - 1) / WPB;
-  dim3 grid(nb), blk(64 * WPB);
-#define LA(CH_, F_) hipLaunchKernelGGL((ln_fwd_kernel<CH_, F_>), grid, blk, 0, st, (const u16*)x, g, b, (u16*)y, mean, \
-                                       rstd, rows, eps, (uint8_t*)q, (const float*)meta, amax_part, (const u16*)r,   \
-                                       (u16*)xsum)
-  if (q) {
-    switch (D) {
-      case 256: LA(1, true); break;
-      case 512: LA(2, true); break;
-      case 768: LA(3, true); break;
-      case 1024: LA(4, true); break;
-      default: return -1;
-    }
-  } else {
-    switch (D) {
-      case 256: LA(1, false); break;
-      case 512: LA(2, false); break;
-      case 768: LA(3, false); break;
-      case 1024: LA(4, false); break;
-      default: return -1;
-    }
-  }
-#undef LA
-  int e = (int)hipGetLastError();
+  const int e = ln_fwd_launch(q != nullptr, x, g, b, y, mean, rstd, rows, D, eps, q, meta, amax_part, r, xsum, st);
   if (e || !q) return e;
-  return pdt_fp8_meta_roll_partial(meta, amax_part, nb, 0, dq_out, st);
+  return pdt_fp8_meta_roll_partial(meta, amax_part, pdt_ln_fwd_f8_blocks(rows), 0, dq_out, st);
 }
 
 // LayerNorm forward that also emits the e4m3 codes of its output for the next fp8 GEMM
@@ -415,31 +403,17 @@ PDT_API int pdt_ln_add_fwd(const void* x, const void* r, void* xsum, const float
 // (codes only).
 PDT_API int pdt_ln_fwd_f8(const void* x, const float* g, const float* b, void* y, float* mean, float* rstd, int rows,
                           int D, float eps, void* q, float* meta, float* amax_part, float* dq_out, hipStream_t st) {
-  const int nb = (rows + WPB - 1) / WPB;
-  dim3 grid(nb), blk(64 * WPB);
-#define LF(CH_) hipLaunchKernelGGL((ln_fwd_kernel<CH_, true>), grid, blk, 0, st, (const u16*)x, g, b, (u16*)y, mean, \
-                                   rstd, rows, eps, (uint8_t*)q, (const float*)meta, amax_part)
-  switch (D) {
-    case 256: LF(1); break;
-    case 512: LF(2); break;
-    case 768: LF(3); break;
-    case 1024: LF(4); break;
-    default: return -1;
-  }
-#undef LF
-  int e = (int)hipGetLastError();
+  const int e = ln_fwd_launch(true, x, g, b, y, mean, rstd, rows, D, eps, q, meta, amax_part, nullptr, nullptr, st);
   if (e) return e;
-  return pdt_fp8_meta_roll_partial(meta, amax_part, nb, 0, dq_out, st);
+  return pdt_fp8_meta_roll_partial(meta, amax_part, pdt_ln_fwd_f8_blocks(rows), 0, dq_out, st);
 }
 
 // rows per LayerNorm-backward block: 64, doubled until at most PDT_LN_BWD_MAXB (512) blocks
 static int ln_rows_per_block(int rows) {
-  static int maxb = -1;
-  if (maxb < 0) {
-    const char* e = getenv("PDT_LN_BWD_MAXB");
-    maxb = e ? atoi(e) : 512;
-    if (maxb < 64) maxb = 512;
-  }
+  static const int maxb = [] {
+    const int v = pdt_env_int("PDT_LN_BWD_MAXB", 512);
+    return v < 64 ? 512 : v;
+  }();
   int rpb = 64;
   while ((rows + rpb - 1) / rpb > maxb) rpb *= 2;
   return rpb;
@@ -451,28 +425,39 @@ PDT_API int pdt_ln_bwd_blocks(int rows) {
   return b < 1 ? 1 : b;
 }
 
+// ln_bwd_kernel<D / 256, f8> over pdt_ln_bwd_blocks(rows) blocks, then the column sums of its
+// partials into dg / db; -1 with nothing launched when D is not covered. The column-sum launch's
+// own error is left to the caller's next check.
+static int ln_bwd_launch(bool f8, const void* dy, const void* x, const float* g, const float* mean, const float* rstd,
+                         void* dx, float* dg, float* db, float* part, int rows, int D, int accumulate,
+                         const void* addend, void* q8, const float* q8_meta, float* q8_part, float* cpart,
+                         hipStream_t st) {
+  const int ch = ln_chunks(D);
+  if (!ch) return -1;
+  const int blocks = pdt_ln_bwd_blocks(rows);
+  const int rpb = ln_rows_per_block(rows);
+  dim3 grid(blocks), blk(64 * WPB);
+  pdt_dispatch<1, 4>(ch, [&](auto n) {
+    constexpr int CH = decltype(n)::value;
+    auto kern = f8 ? ln_bwd_kernel<CH, true> : ln_bwd_kernel<CH, false>;
+    hipLaunchKernelGGL(kern, grid, blk, 0, st, (const u16*)dy, (const u16*)x, g, mean, rstd, (u16*)dx, part, rows, rpb,
+                       (const u16*)addend, (uint8_t*)q8, q8_meta, q8_part, cpart);
+  });
+  const int e = (int)hipGetLastError();
+  if (e) return e;
+  hipLaunchKernelGGL(colsum_f32_kernel, dim3((D + 63) / 64), dim3(64 * CS_RG), 0, st, part, dg, db, blocks, D,
+                     accumulate);
+  return 0;
+}
+
 // addend (optional, bf16 [rows][D]): dx = LN backward + addend (a residual branch's
 // gradient of the same input, summed in the same pass)
 PDT_API int pdt_ln_bwd(const void* dy, const void* x, const float* g, const float* mean, const float* rstd, void* dx,
                        float* dg, float* db, float* part, int rows, int D, int accumulate, const void* addend,
                        hipStream_t st) {
-  const int blocks = pdt_ln_bwd_blocks(rows);
-  const int rpb = ln_rows_per_block(rows);
-  dim3 grid(blocks), blk(64 * WPB);
-  const u16 *DY = (const u16*)dy, *X = (const u16*)x;
-  u16* DX = (u16*)dx;
-  const u16* AD = (const u16*)addend;
-  switch (D) {
-    case 256: hipLaunchKernelGGL(ln_bwd_kernel<1>, grid, blk, 0, st, DY, X, g, mean, rstd, DX, part, rows, rpb, AD); break;
-    case 512: hipLaunchKernelGGL(ln_bwd_kernel<2>, grid, blk, 0, st, DY, X, g, mean, rstd, DX, part, rows, rpb, AD); break;
-    case 768: hipLaunchKernelGGL(ln_bwd_kernel<3>, grid, blk, 0, st, DY, X, g, mean, rstd, DX, part, rows, rpb, AD); break;
-    case 1024: hipLaunchKernelGGL(ln_bwd_kernel<4>, grid, blk, 0, st, DY, X, g, mean, rstd, DX, part, rows, rpb, AD); break;
-    default: return -1;
-  }
-  int e = (int)hipGetLastError();
+  const int e = ln_bwd_launch(false, dy, x, g, mean, rstd, dx, dg, db, part, rows, D, accumulate, addend, nullptr,
+                              nullptr, nullptr, nullptr, st);
   if (e) return e;
-  hipLaunchKernelGGL(colsum_f32_kernel, dim3((D + 63) / 64), dim3(64 * CS_RG), 0, st, part, dg, db, blocks, D,
-                     accumulate);
   PDT_RETURN_LAUNCH();
 }
 
@@ -482,28 +467,10 @@ PDT_API int pdt_ln_bwd(const void* dy, const void* x, const float* g, const floa
 PDT_API int pdt_ln_bwd_f8(const void* dy, const void* x, const float* g, const float* mean, const float* rstd,
                           void* dx, float* dg, float* db, float* part, int rows, int D, int accumulate,
                           const void* addend, void* q8, float* q8_meta, float* q8_part, float* q8_dq, hipStream_t st) {
-  const int blocks = pdt_ln_bwd_blocks(rows);
-  const int rpb = ln_rows_per_block(rows);
-  dim3 grid(blocks), blk(64 * WPB);
-  const u16 *DY = (const u16*)dy, *X = (const u16*)x;
-  u16* DX = (u16*)dx;
-  const u16* AD = (const u16*)addend;
-  uint8_t* Q = (uint8_t*)q8;
-#define LB8(CH_) hipLaunchKernelGGL((ln_bwd_kernel<CH_, true>), grid, blk, 0, st, DY, X, g, mean, rstd, DX, part, rows, \
-                                    rpb, AD, Q, (const float*)q8_meta, q8_part)
-  switch (D) {
-    case 256: LB8(1); break;
-    case 512: LB8(2); break;
-    case 768: LB8(3); break;
-    case 1024: LB8(4); break;
-    default: return -1;
-  }
-#undef LB8
-  int e = (int)hipGetLastError();
+  const int e = ln_bwd_launch(true, dy, x, g, mean, rstd, dx, dg, db, part, rows, D, accumulate, addend, q8, q8_meta,
+                              q8_part, nullptr, st);
   if (e) return e;
-  hipLaunchKernelGGL(colsum_f32_kernel, dim3((D + 63) / 64), dim3(64 * CS_RG), 0, st, part, dg, db, blocks, D,
-                     accumulate);
-  return pdt_fp8_meta_roll_partial(q8_meta, q8_part, blocks, 1, q8_dq, st);
+  return pdt_fp8_meta_roll_partial(q8_meta, q8_part, pdt_ln_bwd_blocks(rows), 1, q8_dq, st);
 }
 
 // pdt_ln_bwd_f8 + the column sums of dx (bf16 as stored) into bias_out [D] (= or += with
@@ -515,27 +482,10 @@ PDT_API int pdt_ln_bwd_f8_db(const void* dy, const void* x, const float* g, cons
                              const void* addend, void* q8, float* q8_meta, float* q8_part, float* q8_dq,
                              float* cpart, float* bias_out, int bias_acc, hipStream_t st) {
   if (!cpart || !bias_out) return -1;
-  const int blocks = pdt_ln_bwd_blocks(rows);
-  const int rpb = ln_rows_per_block(rows);
-  dim3 grid(blocks), blk(64 * WPB);
-  const u16 *DY = (const u16*)dy, *X = (const u16*)x;
-  u16* DX = (u16*)dx;
-  const u16* AD = (const u16*)addend;
-  uint8_t* Q = (uint8_t*)q8;
-#define LB8(CH_) hipLaunchKernelGGL((ln_bwd_kernel<CH_, true>), grid, blk, 0, st, DY, X, g, mean, rstd, DX, part, rows, \
-                                    rpb, AD, Q, (const float*)q8_meta, q8_part, cpart)
-  switch (D) {
-    case 256: LB8(1); break;
-    case 512: LB8(2); break;
-    case 768: LB8(3); break;
-    case 1024: LB8(4); break;
-    default: return -1;
-  }
-#undef LB8
-  int e = (int)hipGetLastError();
+  int e = ln_bwd_launch(true, dy, x, g, mean, rstd, dx, dg, db, part, rows, D, accumulate, addend, q8, q8_meta,
+                        q8_part, cpart, st);
   if (e) return e;
-  hipLaunchKernelGGL(colsum_f32_kernel, dim3((D + 63) / 64), dim3(64 * CS_RG), 0, st, part, dg, db, blocks, D,
-                     accumulate);
+  const int blocks = pdt_ln_bwd_blocks(rows);
   e = pdt_wgrad_reduce_rows(cpart, bias_out, blocks, D, 1.f, bias_acc, cpart + (long)blocks * D, st);
   if (e) return e;
   return pdt_fp8_meta_roll_partial(q8_meta, q8_part, blocks, 1, q8_dq, st);

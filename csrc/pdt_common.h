@@ -6,6 +6,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+
+#include <type_traits>
 
 #include "pdt_api.h"
 
@@ -234,4 +237,42 @@ static inline int pdt_num_cus() {
                                                                                                                : 256;
   }
   return cache[dev];
+}
+
+// Environment switches (A/B runs, tests). Plain getenv parses, nothing cached: a read-once switch
+// is a function-local static at its site, one with a setter a file-scope variable there.
+// A flag that is on by default goes off only with a leading '0', one that is off by default on
+// only with a leading '1'; anything else is the default.
+static inline int pdt_env_flag(const char* name, int dflt) {
+  const char* e = getenv(name);
+  if (e == nullptr) return dflt;
+  return dflt ? e[0] != '0' : e[0] == '1';
+}
+// atoi of the variable, dflt when it is unset; the site clamps / validates
+static inline int pdt_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
+// f(std::integral_constant<int, N>{}) for N = n, LO <= n < HI; every other n takes HI (the
+// `default:` of the ladders this replaces -- callers bound n first). With a generic lambda, one
+// launch statement instantiates a kernel template for LO..HI.
+template <int LO, int HI, class F>
+static inline void pdt_dispatch(int n, F&& f) {
+  if constexpr (LO == HI) {
+    f(std::integral_constant<int, HI>{});
+  } else {
+    if (n == LO) f(std::integral_constant<int, LO>{});
+    else pdt_dispatch<LO + 1, HI>(n, f);
+  }
+}
+
+// the fields every attention parameter struct shares (qkv [B, T, 3, H, 64] bf16, head dim 64)
+template <class P>
+static inline void pdt_attn_fill(P& p, const void* qkv, int B, int T, int H, float scale) {
+  p.qkv = (const u16*)qkv;
+  p.B = B; p.T = T; p.H = H;
+  p.ld = 3L * H * 64;
+  p.ldo = (long)H * 64;
+  p.c = scale * 1.4426950408889634f;  // softmax scale * log2(e)
 }

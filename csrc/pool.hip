@@ -370,8 +370,8 @@ PDT_API int pdt_maxpool_bwd(const void* dy, const void* idx, void* dx, int N, in
                             int k, int s, int p, hipStream_t st) {
   if (C % 8) return -1;
   long total = (long)N * H * W * (C / 8);
-  const char* e = getenv("PDT_MAXPOOL_BWD_ROW");  // "0": always the generic gather kernel (A/B, tests)
-  const bool row_ok = !(e && e[0] == '0');
+  // "0": always the generic gather kernel (A/B, tests); read on every call, tests flip it in-process
+  const bool row_ok = pdt_env_flag("PDT_MAXPOOL_BWD_ROW", 1);
   if (row_ok && k == 3 && s == 2 && p == 1 && Ho == (H + 1) / 2 && Wo == (W + 1) / 2 && C == 64 &&
       (long)N * ((H + 1) / 2) < (1L << 31)) {
     hipLaunchKernelGGL(maxpool_bwd_k3s2_kernel<8>, dim3(N * ((H + 1) / 2)), dim3(NT), 0, st, (const u16*)dy,

@@ -499,11 +499,8 @@ PDT_API int pdt_wgrad_f8_plan(int M, int Mo, int No, int variant, int* ktiles_pe
   int smax = (w.target + tiles - 1) / tiles;
   if (smax > nk) smax = nk;
   if (smax < 1) smax = 1;
-  static int legacy = -1;  // PDT_WG8_PLAN=0: the previous plan, s = ceil(target / tiles) (A/B switch)
-  if (legacy < 0) {
-    const char* e = getenv("PDT_WG8_PLAN");
-    legacy = (e && e[0] == '0') ? 1 : 0;
-  }
+  // PDT_WG8_PLAN=0: the previous plan, s = ceil(target / tiles) (A/B switch)
+  static const int legacy = !pdt_env_flag("PDT_WG8_PLAN", 1);
   if (legacy) {
     int s = smax;
     while (s > 1 && (nk + s - 1) / s * BK < 512) --s;
@@ -557,14 +554,8 @@ PDT_API int pdt_linear_wgrad_f8(const void* dy8, const void* x8, const float* dq
   p.ktiles_per_split = ktiles_per_split;
   const int G = reduce_groups8(splits, Mo, No);
   p.bslab = bias_out ? slab + (long)splits * Mo * No + (G > 1 ? (long)G * Mo * No : 0) : nullptr;
-  {
-    static int xcd_env = -1;
-    if (xcd_env < 0) {
-      const char* e = getenv("PDT_WGRAD_XCD");
-      xcd_env = (e && e[0] == '0') ? 0 : 1;
-    }
-    p.xcd = xcd_env;
-  }
+  static const int xcd_env = pdt_env_flag("PDT_WGRAD_XCD", 1);
+  p.xcd = xcd_env;
   const int tiles = ((Mo + w.BM - 1) / w.BM) * ((No + w.BN - 1) / w.BN);
   dim3 grid(tiles * splits);
   const int lrc = bias_out ? launch8<true>(w, grid, p, stream) : launch8<false>(w, grid, p, stream);

@@ -134,8 +134,22 @@ def test_ln_refuses_other_widths():
                           no._s()) == -1
     assert lib.pdt_ln_bwd(no._p(x), no._p(x), no._p(w), no._p(mean), no._p(rstd), no._p(y), no._p(dg), no._p(db),
                           no._p(part), 4, 384, 0, None, no._s()) == -1
+    # the fp8 / residual-add entry points: nothing launched either (codes, scaling state, partials)
+    xsum, q = G((4, 384), BF, 1.0), G((4, 384), torch.uint8, 1)
+    meta, qpart, dq = G(lib.pdt_fp8_meta_words(), F32, 1.0), G(4, F32, 1.0), G(1, F32, 1.0)
+    cpart, bias = G(384 + lib.pdt_reduce_rows_work(1, 384), F32, 1.0), G(384, F32, 1.0)
+    assert lib.pdt_ln_fwd_f8(no._p(x), no._p(w), no._p(w), no._p(y), no._p(mean), no._p(rstd), 4, 384, LN_EPS,
+                             no._p(q), no._p(meta), no._p(qpart), no._p(dq), no._s()) == -1
+    for codes in (None, q):
+        m, p, d = (no._p(meta), no._p(qpart), no._p(dq)) if codes is not None else (None, None, None)
+        assert lib.pdt_ln_add_fwd(no._p(x), no._p(x), no._p(xsum), no._p(w), no._p(w), no._p(y), no._p(mean),
+                                  no._p(rstd), 4, 384, LN_EPS, no._p(codes), m, p, d, no._s()) == -1
+    bwd = (no._p(x), no._p(x), no._p(w), no._p(mean), no._p(rstd), no._p(y), no._p(dg), no._p(db), no._p(part), 4, 384,
+           0, None, no._p(q), no._p(meta), no._p(qpart), no._p(dq))
+    assert lib.pdt_ln_bwd_f8(*bwd, no._s()) == -1
+    assert lib.pdt_ln_bwd_f8_db(*bwd, no._p(cpart), no._p(bias), 0, no._s()) == -1
     done("refused")
-    for t in (y, mean, rstd, part, dg, db):
+    for t in (y, mean, rstd, part, dg, db, xsum, q, meta, qpart, dq, cpart, bias):
         assert bool((t == 1).all())
 
 
