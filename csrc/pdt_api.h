@@ -149,6 +149,10 @@ PDT_API int pdt_wgrad_reduce_rows(const float* rows, float* out, int nrows, int 
 PDT_API int pdt_wgrad_reduce(float* slab, float* out, const float* bslab, float* bias_out, int splits, int Mo, int No,
                              float scale, int accumulate, hipStream_t stream);
 
+// ema.hip
+PDT_API int pdt_ema_update(const void* chunks, int nchunks, void* ema, const void* src, void* shadows, float* dev,
+                           float decay, int warmup, hipStream_t st);
+
 // fp8.hip
 PDT_API int pdt_amax_blocks(long n);
 PDT_API int pdt_amax_partial(const void* x, int bf16, long n, float* partial, hipStream_t st);

@@ -16,6 +16,11 @@ with ``torch.load(weights_only=True)``; Q17 ``arch`` is the unwrapped model
 class; the LR-scheduler state is saved too (extra key ``lr_scheduler``) and
 restored on resume; checkpoint writes are atomic (tmp + rename); the
 early-stop vote is one broadcast from rank 0 instead of a pickled all-gather.
+
+With a weight EMA (``trainer.ema``, ``optim.ModelEMA``) a checkpoint gains two keys,
+``state_dict_ema`` (the averaged weights under the model's own names) and ``ema``
+(``{num_updates, decay, warmup}``), both restored on resume; a checkpoint without them starts
+the average from the loaded weights. Without an EMA no key is added.
 """
 from __future__ import annotations
 
@@ -34,7 +39,7 @@ def unwrap_model(model):
 
 
 class BaseTrainer:
-    def __init__(self, model, criterion, metric_ftns, optimizer, config, lr_scheduler=None):
+    def __init__(self, model, criterion, metric_ftns, optimizer, config, lr_scheduler=None, ema=None):
         self.config = config
         self.logger = config.get_logger("trainer", config["trainer"]["verbosity"])
 
@@ -43,6 +48,7 @@ class BaseTrainer:
         self.metric_ftns = metric_ftns
         self.optimizer = optimizer
         self.lr_scheduler = lr_scheduler
+        self.ema = ema  # (before the resume below, which restores it)
 
         cfg_trainer = config["trainer"]
         self.epochs = cfg_trainer["epochs"]
@@ -132,6 +138,10 @@ class BaseTrainer:
         }
         if self.lr_scheduler is not None:
             state["lr_scheduler"] = self.lr_scheduler.state_dict()
+        if self.ema is not None:
+            ema_state = self.ema.state_dict()
+            state["state_dict_ema"] = ema_state.pop("state_dict")
+            state["ema"] = ema_state
         return state
 
     @staticmethod
@@ -161,6 +171,14 @@ class BaseTrainer:
             self.logger.warning("Warning: Architecture configuration given in config file is different from that "
                                 "of checkpoint. This may yield an exception while state_dict is being loaded.")
         unwrap_model(self.model).load_state_dict(strip_module_prefix(checkpoint["state_dict"]))
+        if self.ema is not None:
+            if "state_dict_ema" in checkpoint:
+                self.ema.load_state_dict(dict(checkpoint.get("ema", {}),
+                                              state_dict=strip_module_prefix(checkpoint["state_dict_ema"])))
+            else:
+                self.logger.warning("Warning: the checkpoint holds no averaged weights (state_dict_ema); the "
+                                    "EMA starts from the loaded weights.")
+                self.ema.set_to(self.model)
 
         if checkpoint["config"]["optimizer"]["type"] != self.config["optimizer"]["type"]:
             self.logger.warning("Warning: Optimizer type given in config file is different from that of "

@@ -261,6 +261,22 @@ class _FusedBase(Optimizer):
                 sh.copy_(p.detach())
                 _ops().register_shadow(p, sh)
 
+    def mark_updated(self):
+        """Tell the host that the parameters changed without a ``step()`` it ran: replays of a HIP
+        graph that captured ``step()`` rewrite parameters and bf16 shadows on the device, but
+        advance no version counter, so an eager forward afterwards would read weights derived at
+        an older version (space-to-depth, padded, transposed and fp8 weight copies are cached per
+        ``_version``). Bumps every parameter's version and registers the shadows again (they are
+        current: the replays wrote them). Call it before an eager forward that follows replays."""
+        for group in self.param_groups:
+            params = list(group["params"])
+            _bump_versions(params)
+            if self.write_bf16_shadow:
+                for p in params:
+                    sh = self._shadows.get(id(p))
+                    if sh is not None and sh.data_ptr() != 0 and sh.shape == p.shape:
+                        _ops().register_shadow(p, sh)
+
     def refresh_scalars(self):
         """Write each group's current lr into its device scalars (capturable mode): call it
         before replaying a graph that captured ``step()`` -- an LR scheduler changes only the

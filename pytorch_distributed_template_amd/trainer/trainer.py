@@ -27,7 +27,16 @@ MI355X-first changes to the hot loop:
     HIP graph and replayed for every later full-size batch (copied into the graph's
     static input buffers -- the images and the target, which is the labels or, for a mixed
     batch, the three tensors of a ``MixedTarget``); the optimizer is capturable, so replays use the scheduler's
-    current lr and Adam's current step. Partial batches and validation run eagerly.
+    current lr and Adam's current step. Partial batches and validation run eagerly;
+  * ``trainer.ema`` (``{decay, warmup, validate}``, ``optim.ModelEMA`` built by
+    ``runtime.build_ema``): the weight average is updated right after ``optimizer.step()``, in
+    the eager loop and in the captured step alike (one more launch in the graph; the warm-up
+    steps build its tables). ``validate``: ``"both"`` (default) reports ``val_*`` for the trained
+    weights and ``val_ema_*`` for the averaged ones, ``"ema"`` / ``"model"`` only one of them;
+    ``monitor`` may name ``val_ema_<metric>``. Absent or null, nothing changes;
+  * ``trainer.lr_step``: ``"epoch"`` (default, the reference's) or ``"iteration"`` -- the
+    scheduler steps after every optimizer step, graph replays included (the host value; a
+    capturable optimizer's ``refresh_scalars()`` carries it to the device before each replay).
 """
 from __future__ import annotations
 
@@ -109,8 +118,8 @@ class _LossCurve:
 class Trainer(BaseTrainer):
     def __init__(self, model, criterion, metric_ftns, optimizer, config, device,
                  data_loader, valid_data_loader=None, lr_scheduler=None, len_epoch=None,
-                 autocast_dtype=None, channels_last=False):
-        super().__init__(model, criterion, metric_ftns, optimizer, config, lr_scheduler=lr_scheduler)
+                 autocast_dtype=None, channels_last=False, ema=None):
+        super().__init__(model, criterion, metric_ftns, optimizer, config, lr_scheduler=lr_scheduler, ema=ema)
         self.device = device
         self.data_loader = data_loader
         self._base_loader = data_loader
@@ -129,6 +138,15 @@ class Trainer(BaseTrainer):
         self.train_metrics = MetricTracker("loss", writer=self.writer)
         self.loss_curve = _LossCurve(self.writer, device, config["trainer"].get("tensorboard", False))
         self.valid_metrics = MetricTracker("loss", *[m.__name__ for m in self.metric_ftns], writer=self.writer)
+        self.valid_ema_metrics = None
+        self.ema_validate = "model"
+        if self.ema is not None:
+            self.ema_validate = getattr(self.ema, "validate", "both")  # (checked by runtime.build_ema)
+            self.valid_ema_metrics = MetricTracker("ema_loss", *["ema_" + m.__name__ for m in self.metric_ftns],
+                                                   writer=self.writer)
+        self.lr_step = config["trainer"].get("lr_step", "epoch")
+        if self.lr_step not in ("epoch", "iteration"):
+            raise ValueError(f'trainer.lr_step must be "epoch" or "iteration", got {self.lr_step!r}')
         self.last_throughput = None
         # optional per-phase device timing (HIP events + ROCTx ranges): trainer.profile_phases
         self.phase_timer = PhaseTimer(enabled=bool(config["trainer"].get("profile_phases", False))
@@ -142,6 +160,8 @@ class Trainer(BaseTrainer):
         self._graph = None
         self._graph_io = None  # (static data, static target, static loss)
         self._graph_eager_steps = 0
+        # whose weights graph replays have rewritten since their last eager forward (see _valid_epoch)
+        self._replayed = {"model": False, "ema": False}
         # the capture side stream: the one DDP was built on (runtime.builder.wrap_model), if any
         self._side = (getattr(model, "_pdt_capture_stream", None) or torch.cuda.Stream(device=device)) \
             if self.hip_graph else None
@@ -198,6 +218,11 @@ class Trainer(BaseTrainer):
                     loss.backward()
                 with pt.phase("optimizer"):
                     self.optimizer.step()
+                if self.ema is not None:
+                    with pt.phase("ema"):
+                        self.ema.update(self.model)
+            if self.lr_scheduler is not None and self.lr_step == "iteration":
+                self.lr_scheduler.step()
 
             loss_sum += loss.detach().float()
             n_iter += 1
@@ -240,11 +265,16 @@ class Trainer(BaseTrainer):
             log.update({f"ms_{k}": round(v, 3) for k, v in self.phase_timer.summary().items()})
 
         if self.do_validation:
-            val_log = self._valid_epoch(epoch)
-            if pdist.is_main_process():
-                log.update(**{"val_" + k: v for k, v in val_log.items()})
+            if self.ema_validate != "ema":
+                val_log = self._valid_epoch(epoch)
+                if pdist.is_main_process():
+                    log.update(**{"val_" + k: v for k, v in val_log.items()})
+            if self.ema is not None and self.ema_validate != "model":
+                val_log = self._valid_epoch(epoch, model=self.ema.module, prefix="ema_")
+                if pdist.is_main_process():
+                    log.update(**{"val_" + k: v for k, v in val_log.items()})
 
-        if self.lr_scheduler is not None:
+        if self.lr_scheduler is not None and self.lr_step == "epoch":
             self.lr_scheduler.step()
         return log
 
@@ -260,6 +290,8 @@ class Trainer(BaseTrainer):
             loss = self.criterion(output, target)
         loss.backward()
         self.optimizer.step()
+        if self.ema is not None:
+            self.ema.update(self.model)
         return loss
 
     def _graph_step(self, data, target):
@@ -290,6 +322,7 @@ class Trainer(BaseTrainer):
                     static.copy_(t)
             self.optimizer.refresh_scalars()  # the scheduler's lr (written outside the graph)
             self._graph.replay()
+            self._replayed["model"] = self._replayed["ema"] = True
             return io[2]
         side.wait_stream(cur)
         with torch.cuda.stream(side):
@@ -322,16 +355,29 @@ class Trainer(BaseTrainer):
 
     # ------------------------------------------------------------------ validate
     @torch.no_grad()
-    def _valid_epoch(self, epoch):
-        self.model.eval()
-        self.valid_metrics.reset()
+    def _valid_epoch(self, epoch, model=None, prefix=""):
+        """Validate ``model`` (default: the trained one); the averaged weights' pass (``prefix``
+        ``"ema_"``) keeps its own tracker, so its keys are ``ema_loss`` / ``ema_<metric>``."""
+        model = self.model if model is None else model
+        tracker = self.valid_metrics if not prefix else self.valid_ema_metrics
+        # graph replays rewrite weights (and their bf16 shadows) on the device without a host-side
+        # version bump: without one this eager forward would read the weight copies the kernel
+        # layer cached per version at the previous validation (stem, padded, fp8, transposed)
+        who = "model" if model is self.model else "ema" if self.ema is not None and model is self.ema.module else None
+        if who is not None and self._replayed[who]:
+            owner = self.optimizer if who == "model" else self.ema
+            if hasattr(owner, "mark_updated"):
+                owner.mark_updated()
+            self._replayed[who] = False
+        model.eval()
+        tracker.reset()
         outputs, targets = [], []
         loss_sum = torch.zeros((), dtype=torch.float64, device=self.device)
         n = 0
         for data, target in self.valid_data_loader:
             data, target = self._to_device(data, target)
             with self._autocast():
-                output = self.model(data)
+                output = model(data)
                 loss = self.criterion(output, target)
             loss_sum += loss.double() * data.shape[0]
             n += data.shape[0]
@@ -351,11 +397,12 @@ class Trainer(BaseTrainer):
         if pdist.is_main_process():
             out_all = torch.cat(out_all)
             tgt_all = torch.cat(tgt_all)
-            self.valid_metrics.update("loss", float(stats[0] / max(stats[1], 1)))
+            tracker.update(prefix + "loss", float(stats[0] / max(stats[1], 1)))
             for met in self.metric_ftns:
-                self.valid_metrics.update(met.__name__, met(out_all, tgt_all))
-            result = self.valid_metrics.result()
-        self.model.train()
+                tracker.update(prefix + met.__name__, met(out_all, tgt_all))
+            result = tracker.result()
+        if model is self.model:
+            model.train()
         return result
 
     def _progress(self, batch_idx):

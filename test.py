@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Evaluation entry point -- same CLI as the reference ``/root/reference/test.py:104-128``.
 
-    python test.py -r path/to/checkpoint-epochN.pth [-c override.json] [-s save_dir] [--seed N]
+    python test.py -r path/to/checkpoint-epochN.pth [-c override.json] [-s save_dir] [--seed N] [--ema]
+
+``--ema`` evaluates the averaged weights (``state_dict_ema``, written when ``trainer.ema`` is on).
 
 Loads the checkpoint (``torch.load(weights_only=True)``: our checkpoints hold
 only tensors and plain dicts), runs distributed inference over
@@ -33,7 +35,12 @@ def main(args, config, device):
         logger.info(model)
         logger.info("Loading checkpoint: {} ...".format(config.resume))
     checkpoint = load_checkpoint(config.resume, map_location=device)
-    model.load_state_dict(strip_module_prefix(checkpoint["state_dict"]))
+    args_ema = bool(getattr(args, "ema", False))
+    key = "state_dict_ema" if args_ema else "state_dict"
+    if args_ema and key not in checkpoint:
+        raise KeyError("--ema: the checkpoint {} holds no averaged weights (state_dict_ema); it was written "
+                       "without trainer.ema".format(config.resume))
+    model.load_state_dict(strip_module_prefix(checkpoint[key]))
     model.eval()
 
     ac = autocast_dtype(config, device)
@@ -76,6 +83,8 @@ def cli(argv=None):
     args.add_argument("--seed", type=int, default=None, help="Random seed.")
     args.add_argument("--deterministic", action="store_true")
     args.add_argument("--backend", default=None, choices=["auto", "native", "torch"])
+    args.add_argument("--ema", action="store_true",
+                      help="evaluate the averaged weights (state_dict_ema) instead of the trained ones")
     ns = args.parse_args(argv)
     assert ns.resume is not None, "Testing mode requires model path!"
     device = pdist.init_distributed(ns.local_rank)

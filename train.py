@@ -17,8 +17,8 @@ import torch
 
 from pytorch_distributed_template_amd.config import ConfigParser
 from pytorch_distributed_template_amd.runtime import (autocast_dtype, build_criterion_metrics, build_loader,
-                                                      build_model, build_optimizer, pretune_model,
-                                                      wrap_model)
+                                                      build_ema, build_model, build_optimizer,
+                                                      pretune_model, wrap_model)
 from pytorch_distributed_template_amd.trainer import Trainer
 from pytorch_distributed_template_amd.utils import dist as pdist
 from pytorch_distributed_template_amd.utils.util import seed_everything, set_deterministic
@@ -30,6 +30,7 @@ def main(args, config, device):
     model = build_model(config, device)
     criterion, metrics = build_criterion_metrics(config)
     optimizer, lr_scheduler = build_optimizer(config, model)
+    ema = build_ema(config, model)  # (the unwrapped model, before its first forward)
 
     data_loader = build_loader(config, "train_loader")
     valid_data_loader = None if args.no_validate else build_loader(config, "valid_loader")
@@ -46,7 +47,7 @@ def main(args, config, device):
     trainer = Trainer(model, criterion, metrics, optimizer, config=config, device=device,
                       data_loader=data_loader, valid_data_loader=valid_data_loader, lr_scheduler=lr_scheduler,
                       len_epoch=tcfg.get("len_epoch"), autocast_dtype=autocast_dtype(config, device),
-                      channels_last=tcfg.get("channels_last", False))
+                      channels_last=tcfg.get("channels_last", False), ema=ema)
     trainer.train()
     return trainer
 
