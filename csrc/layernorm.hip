@@ -27,7 +27,12 @@ __device__ __forceinline__ void st4(u16* p, const float* f) {
 // meta[0] of the consuming fp8 GEMM, and the block's |y| max to amax_part[blockIdx.x]
 // (rolled into that GEMM's amax history by pdt_fp8_meta_roll_partial) -- the
 // activation-quantisation pass of the fp8 path folded into the producer.
-template <int CH, bool F8 = false>  // chunks of 4 per lane: D = 256*CH
+// DP (stochastic depth, with radd): xsum = bf16(r + dscale[row / rps] * x), the branch x scaled per
+// sample by 0 or 1/keep (csrc/drop_path.hip). The scale is wave-uniform (one wave per row): it
+// is read through a scalar register and decided once per row, outside the chunk loops -- a
+// dropped sample's branch is never loaded (its values, NaN or Inf included, cannot reach xsum,
+// which holds r's bits) and costs no read.
+template <int CH, bool F8 = false, bool DP = false>  // chunks of 4 per lane: D = 256*CH
 __global__ void __launch_bounds__(64 * WPB) ln_fwd_kernel(const u16* __restrict__ x, const float* __restrict__ g,
                                                           const float* __restrict__ b, u16* __restrict__ y,
                                                           float* __restrict__ mean_out, float* __restrict__ rstd_out,
@@ -35,7 +40,8 @@ __global__ void __launch_bounds__(64 * WPB) ln_fwd_kernel(const u16* __restrict_
                                                           const float* __restrict__ meta = nullptr,
                                                           float* __restrict__ amax_part = nullptr,
                                                           const u16* __restrict__ radd = nullptr,
-                                                          u16* __restrict__ xsum = nullptr) {
+                                                          u16* __restrict__ xsum = nullptr,
+                                                          const float* __restrict__ dscale = nullptr, int rps = 1) {
   const int lane = threadIdx.x & 63;
   int row = blockIdx.x * WPB + (threadIdx.x >> 6);
   __shared__ float red[WPB];
@@ -52,7 +58,30 @@ __global__ void __launch_bounds__(64 * WPB) ln_fwd_kernel(const u16* __restrict_
   // block: with the residual branch inside the chunk loop (or between the x and r loads) hipcc
   // waited for the x loads before issuing the r loads
   uint2 xw[CH], rw[CH];
-  if (radd != nullptr) {  // residual add of a pre-norm block: xsum = bf16(x + r), normalised
+  if constexpr (DP) {
+    const float sc = dscale[__builtin_amdgcn_readfirstlane(row) / rps];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) rw[c] = *reinterpret_cast<const uint2*>(radd + (long)row * D + (c * 64 + lane) * 4);
+    if (sc != 0.f) {
+#pragma unroll
+      for (int c = 0; c < CH; ++c) xw[c] = *reinterpret_cast<const uint2*>(xr + (c * 64 + lane) * 4);
+#pragma unroll
+      for (int c = 0; c < CH; ++c) {
+        const float r[4] = {lo_bf(rw[c].x), hi_bf(rw[c].x), lo_bf(rw[c].y), hi_bf(rw[c].y)};
+        const float xv[4] = {lo_bf(xw[c].x), hi_bf(xw[c].x), lo_bf(xw[c].y), hi_bf(xw[c].y)};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[c][e] = bf2f(f2bf(fmaf(sc, xv[e], r[e])));
+        st4(xsum + (long)row * D + (c * 64 + lane) * 4, v[c]);
+      }
+    } else {  // dropped sample: xsum = r, bit for bit
+#pragma unroll
+      for (int c = 0; c < CH; ++c) {
+        v[c][0] = lo_bf(rw[c].x); v[c][1] = hi_bf(rw[c].x);
+        v[c][2] = lo_bf(rw[c].y); v[c][3] = hi_bf(rw[c].y);
+        *reinterpret_cast<uint2*>(xsum + (long)row * D + (c * 64 + lane) * 4) = rw[c];
+      }
+    }
+  } else if (radd != nullptr) {  // residual add of a pre-norm block: xsum = bf16(x + r), normalised
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
       xw[c] = *reinterpret_cast<const uint2*>(xr + (c * 64 + lane) * 4);
@@ -129,7 +158,12 @@ __global__ void __launch_bounds__(64 * WPB) ln_fwd_kernel(const u16* __restrict_
 // F8: also write the e5m2 codes of dx (bf16-rounded) with the delayed scale q8_meta[0]
 // of the fp8 GEMM that consumes this gradient, and the block's max |dx| to
 // q8_part[blockIdx.x] (the e5m2 quantisation pass of that GEMM folded in here).
-template <int CH, bool F8 = false>
+// DP (stochastic depth): the input was r + dscale[row / rps] * y (ln_fwd_kernel DP). dx is the
+// residual stream's gradient, unchanged; the branch's gradient dyb = bf16(scale * dx as stored),
+// +0 on the rows of a dropped sample (selected, not multiplied), is written beside it, and the
+// e5m2 codes, their amax and the column sums cpart are taken from dyb -- they belong to the layer
+// that produced y. The row's scale is one more load of the prefetch.
+template <int CH, bool F8 = false, bool DP = false>
 __global__ void __launch_bounds__(64 * WPB) ln_bwd_kernel(const u16* __restrict__ dy, const u16* __restrict__ x,
                                                           const float* __restrict__ g,
                                                           const float* __restrict__ mean_in,
@@ -139,7 +173,9 @@ __global__ void __launch_bounds__(64 * WPB) ln_bwd_kernel(const u16* __restrict_
                                                           uint8_t* __restrict__ q8 = nullptr,
                                                           const float* __restrict__ q8_meta = nullptr,
                                                           float* __restrict__ q8_part = nullptr,
-                                                          float* __restrict__ cpart = nullptr) {
+                                                          float* __restrict__ cpart = nullptr,
+                                                          const float* __restrict__ dscale = nullptr, int rps = 1,
+                                                          u16* __restrict__ dyb = nullptr) {
   // cpart (optional): per-block column sums of dx as stored (bf16) -> cpart[blockIdx.x][D]: the
   // bias gradient of the layer whose output gradient dx is, formed where dx is written
   constexpr int D = 256 * CH;
@@ -162,7 +198,7 @@ __global__ void __launch_bounds__(64 * WPB) ln_bwd_kernel(const u16* __restrict_
   // loads and stores both pending it waits for zero -- which, at a wait for this row's data
   // placed after the prefetch, would have drained the prefetch too).
   uint2 nx[CH], ndy[CH], nad[CH];
-  float nmean = 0.f, nrstd = 0.f;
+  float nmean = 0.f, nrstd = 0.f, nsc = 0.f;
   // (without an addend the third stream re-reads dy -- a valid address, its values unused --
   // so the prefetch is one branch-free block of loads)
   const u16* aptr = addend != nullptr ? addend : dy;
@@ -176,6 +212,7 @@ __global__ void __launch_bounds__(64 * WPB) ln_bwd_kernel(const u16* __restrict_
     }
     nmean = mean_in[rr];
     nrstd = rstd_in[rr];
+    if constexpr (DP) nsc = dscale[rr / rps];
   };
   // gamma is per column: loaded once (a load issued after the prefetch and waited for inside
   // the row would retire the prefetch with it -- vmcnt counts in order)
@@ -187,6 +224,8 @@ __global__ void __launch_bounds__(64 * WPB) ln_bwd_kernel(const u16* __restrict_
 #pragma unroll
     for (int c = 0; c < CH; ++c) asm volatile("" : "+v"(nx[c]), "+v"(ndy[c]), "+v"(nad[c])::"memory");
     asm volatile("" : "+v"(nmean), "+v"(nrstd)::"memory");
+    if constexpr (DP) asm volatile("" : "+v"(nsc)::"memory");
+    const float sc = nsc;
     uint2 cx[CH], cdy[CH], cad[CH];
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
@@ -226,6 +265,11 @@ __global__ void __launch_bounds__(64 * WPB) ln_bwd_kernel(const u16* __restrict_
         for (int e = 0; e < 4; ++e) o[e] += ad[c][e];
       }
       st4(dx + (long)row * D + (c * 64 + lane) * 4, o);
+      if constexpr (DP) {  // from here on o is the branch gradient: what is stored, summed and coded
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = sc != 0.f ? sc * bf2f(f2bf(o[e])) : 0.f;
+        st4(dyb + (long)row * D + (c * 64 + lane) * 4, o);
+      }
       if (cpart != nullptr) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) cs[c][e] += bf2f(f2bf(o[e]));
@@ -361,18 +405,20 @@ __global__ void gelu_bwd_kernel(const u16* __restrict__ dy, const u16* __restric
 // chunks of 4 per lane of the instantiation for width D (D = 256, 512, 768, 1024); 0: not covered
 static int ln_chunks(int D) { return (D % 256 == 0 && D >= 256 && D <= 1024) ? D / 256 : 0; }
 
-// ln_fwd_kernel<D / 256, f8>, one wave per row; -1 with nothing launched when D is not covered
+// ln_fwd_kernel<D / 256, f8, dscale != nullptr>, one wave per row; -1 with nothing launched when D
+// is not covered. dscale / rps: the per-sample branch scales of the drop-path instantiation.
 static int ln_fwd_launch(bool f8, const void* x, const float* g, const float* b, void* y, float* mean, float* rstd,
                          int rows, int D, float eps, void* q, const float* meta, float* amax_part, const void* r,
-                         void* xsum, hipStream_t st) {
+                         void* xsum, hipStream_t st, const float* dscale = nullptr, int rps = 1) {
   const int ch = ln_chunks(D);
   if (!ch) return -1;
   dim3 grid((rows + WPB - 1) / WPB), blk(64 * WPB);
   pdt_dispatch<1, 4>(ch, [&](auto n) {
     constexpr int CH = decltype(n)::value;
-    auto kern = f8 ? ln_fwd_kernel<CH, true> : ln_fwd_kernel<CH, false>;
+    auto kern = dscale ? (f8 ? ln_fwd_kernel<CH, true, true> : ln_fwd_kernel<CH, false, true>)
+                       : (f8 ? ln_fwd_kernel<CH, true> : ln_fwd_kernel<CH, false>);
     hipLaunchKernelGGL(kern, grid, blk, 0, st, (const u16*)x, g, b, (u16*)y, mean, rstd, rows, eps, (uint8_t*)q, meta,
-                       amax_part, (const u16*)r, (u16*)xsum);
+                       amax_part, (const u16*)r, (u16*)xsum, dscale, rps);
   });
   return (int)hipGetLastError();
 }
@@ -393,6 +439,21 @@ PDT_API int pdt_ln_add_fwd(const void* x, const void* r, void* xsum, const float
                            float* amax_part, float* dq_out, hipStream_t st) {
   if (!r || !xsum || (q && (!meta || !amax_part)) || (!q && !y)) return -1;
   const int e = ln_fwd_launch(q != nullptr, x, g, b, y, mean, rstd, rows, D, eps, q, meta, amax_part, r, xsum, st);
+  if (e || !q) return e;
+  return pdt_fp8_meta_roll_partial(meta, amax_part, pdt_ln_fwd_f8_blocks(rows), 0, dq_out, st);
+}
+
+// pdt_ln_add_fwd with the branch x scaled per sample (stochastic depth):
+// xsum = bf16(r + scale[row / rows_per_sample] * x); scale holds (rows + rows_per_sample - 1) /
+// rows_per_sample floats, each 0 or 1/keep (one row of pdt_drop_path_scales' table). Where the
+// scale is 0, x is not read and xsum holds r's bits. Everything else as pdt_ln_add_fwd.
+PDT_API int pdt_ln_add_dp_fwd(const void* x, const void* r, void* xsum, const float* g, const float* b, void* y,
+                              float* mean, float* rstd, int rows, int D, float eps, void* q, float* meta,
+                              float* amax_part, float* dq_out, const float* scale, int rows_per_sample,
+                              hipStream_t st) {
+  if (!r || !xsum || (q && (!meta || !amax_part)) || (!q && !y) || !scale || rows_per_sample < 1) return -1;
+  const int e = ln_fwd_launch(q != nullptr, x, g, b, y, mean, rstd, rows, D, eps, q, meta, amax_part, r, xsum, st,
+                              scale, rows_per_sample);
   if (e || !q) return e;
   return pdt_fp8_meta_roll_partial(meta, amax_part, pdt_ln_fwd_f8_blocks(rows), 0, dq_out, st);
 }
@@ -425,13 +486,13 @@ PDT_API int pdt_ln_bwd_blocks(int rows) {
   return b < 1 ? 1 : b;
 }
 
-// ln_bwd_kernel<D / 256, f8> over pdt_ln_bwd_blocks(rows) blocks, then the column sums of its
+// ln_bwd_kernel<D / 256, f8, dscale != nullptr> over pdt_ln_bwd_blocks(rows) blocks, then the column sums of its
 // partials into dg / db; -1 with nothing launched when D is not covered. The column-sum launch's
 // own error is left to the caller's next check.
 static int ln_bwd_launch(bool f8, const void* dy, const void* x, const float* g, const float* mean, const float* rstd,
                          void* dx, float* dg, float* db, float* part, int rows, int D, int accumulate,
                          const void* addend, void* q8, const float* q8_meta, float* q8_part, float* cpart,
-                         hipStream_t st) {
+                         hipStream_t st, const float* dscale = nullptr, int rps = 1, void* dyb = nullptr) {
   const int ch = ln_chunks(D);
   if (!ch) return -1;
   const int blocks = pdt_ln_bwd_blocks(rows);
@@ -439,9 +500,10 @@ static int ln_bwd_launch(bool f8, const void* dy, const void* x, const float* g,
   dim3 grid(blocks), blk(64 * WPB);
   pdt_dispatch<1, 4>(ch, [&](auto n) {
     constexpr int CH = decltype(n)::value;
-    auto kern = f8 ? ln_bwd_kernel<CH, true> : ln_bwd_kernel<CH, false>;
+    auto kern = dscale ? (f8 ? ln_bwd_kernel<CH, true, true> : ln_bwd_kernel<CH, false, true>)
+                       : (f8 ? ln_bwd_kernel<CH, true> : ln_bwd_kernel<CH, false>);
     hipLaunchKernelGGL(kern, grid, blk, 0, st, (const u16*)dy, (const u16*)x, g, mean, rstd, (u16*)dx, part, rows, rpb,
-                       (const u16*)addend, (uint8_t*)q8, q8_meta, q8_part, cpart);
+                       (const u16*)addend, (uint8_t*)q8, q8_meta, q8_part, cpart, dscale, rps, (u16*)dyb);
   });
   const int e = (int)hipGetLastError();
   if (e) return e;
@@ -488,6 +550,30 @@ PDT_API int pdt_ln_bwd_f8_db(const void* dy, const void* x, const float* g, cons
   const int blocks = pdt_ln_bwd_blocks(rows);
   e = pdt_wgrad_reduce_rows(cpart, bias_out, blocks, D, 1.f, bias_acc, cpart + (long)blocks * D, st);
   if (e) return e;
+  return pdt_fp8_meta_roll_partial(q8_meta, q8_part, blocks, 1, q8_dq, st);
+}
+
+// LayerNorm backward of xsum = r + scale[row / rows_per_sample] * y (pdt_ln_add_dp_fwd): dx (the
+// gradient of r, exactly what pdt_ln_bwd writes) and dyb = bf16(scale * dx as stored), the
+// gradient of y, +0 on dropped samples. Optional, as pdt_ln_bwd_f8 / pdt_ln_bwd_f8_db but taken
+// from dyb: q8 (with q8_meta / q8_part / q8_dq) its e5m2 codes and rolled history; cpart (with
+// q8; and bias_out / bias_acc) its column sums, the bias gradient of the layer that produced y.
+PDT_API int pdt_ln_dp_bwd(const void* dy, const void* x, const float* g, const float* mean, const float* rstd,
+                          void* dx, void* dyb, float* dg, float* db, float* part, int rows, int D, int accumulate,
+                          const void* addend, const float* scale, int rows_per_sample, void* q8, float* q8_meta,
+                          float* q8_part, float* q8_dq, float* cpart, float* bias_out, int bias_acc,
+                          hipStream_t st) {
+  if (!dyb || !scale || rows_per_sample < 1 || (q8 && (!q8_meta || !q8_part)) || (cpart && (!q8 || !bias_out)))
+    return -1;
+  int e = ln_bwd_launch(q8 != nullptr, dy, x, g, mean, rstd, dx, dg, db, part, rows, D, accumulate, addend, q8,
+                        q8_meta, q8_part, cpart, st, scale, rows_per_sample, dyb);
+  if (e) return e;
+  if (!q8) PDT_RETURN_LAUNCH();
+  const int blocks = pdt_ln_bwd_blocks(rows);
+  if (cpart) {
+    e = pdt_wgrad_reduce_rows(cpart, bias_out, blocks, D, 1.f, bias_acc, cpart + (long)blocks * D, st);
+    if (e) return e;
+  }
   return pdt_fp8_meta_roll_partial(q8_meta, q8_part, blocks, 1, q8_dq, st);
 }
 

@@ -149,6 +149,10 @@ PDT_API int pdt_wgrad_reduce_rows(const float* rows, float* out, int nrows, int 
 PDT_API int pdt_wgrad_reduce(float* slab, float* out, const float* bslab, float* bias_out, int splits, int Mo, int No,
                              float scale, int accumulate, hipStream_t stream);
 
+// drop_path.hip
+PDT_API int pdt_drop_path_scales(float* scale, int* state, const float* p, const float* inv_keep, int n_branches,
+                                 int B, long sample0, hipStream_t st);
+
 // ema.hip
 PDT_API int pdt_ema_update(const void* chunks, int nchunks, void* ema, const void* src, void* shadows, float* dev,
                            float decay, int warmup, hipStream_t st);
@@ -206,6 +210,10 @@ PDT_API int pdt_ln_fwd_f8_blocks(int rows);
 PDT_API int pdt_ln_add_fwd(const void* x, const void* r, void* xsum, const float* g, const float* b, void* y,
                            float* mean, float* rstd, int rows, int D, float eps, void* q, float* meta,
                            float* amax_part, float* dq_out, hipStream_t st);
+PDT_API int pdt_ln_add_dp_fwd(const void* x, const void* r, void* xsum, const float* g, const float* b, void* y,
+                              float* mean, float* rstd, int rows, int D, float eps, void* q, float* meta,
+                              float* amax_part, float* dq_out, const float* scale, int rows_per_sample,
+                              hipStream_t st);
 PDT_API int pdt_ln_fwd_f8(const void* x, const float* g, const float* b, void* y, float* mean, float* rstd, int rows,
                           int D, float eps, void* q, float* meta, float* amax_part, float* dq_out, hipStream_t st);
 PDT_API int pdt_ln_bwd_blocks(int rows);
@@ -219,6 +227,11 @@ PDT_API int pdt_ln_bwd_f8_db(const void* dy, const void* x, const float* g, cons
                              void* dx, float* dg, float* db, float* part, int rows, int D, int accumulate,
                              const void* addend, void* q8, float* q8_meta, float* q8_part, float* q8_dq, float* cpart,
                              float* bias_out, int bias_acc, hipStream_t st);
+PDT_API int pdt_ln_dp_bwd(const void* dy, const void* x, const float* g, const float* mean, const float* rstd,
+                          void* dx, void* dyb, float* dg, float* db, float* part, int rows, int D, int accumulate,
+                          const void* addend, const float* scale, int rows_per_sample, void* q8, float* q8_meta,
+                          float* q8_part, float* q8_dq, float* cpart, float* bias_out, int bias_acc,
+                          hipStream_t st);
 PDT_API int pdt_gelu_bwd(const void* dy, const void* z, void* dz, long n, hipStream_t st);
 
 // lenet.hip

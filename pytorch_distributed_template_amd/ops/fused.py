@@ -178,15 +178,50 @@ def ln_fork(x, ln: nn.LayerNorm, fp8_for: nn.Linear | None = None, grad_fp8_for:
     return x, ln(x)
 
 
-def ln_add_fork(y, r, ln: nn.LayerNorm, fp8_for: nn.Linear | None = None, grad_fp8_for: nn.Linear | None = None):
+def ln_add_fork(y, r, ln: nn.LayerNorm, fp8_for: nn.Linear | None = None, grad_fp8_for: nn.Linear | None = None,
+                scale=None, rows_per_sample: int | None = None):
     """(y + r, ln(y + r)): :func:`ln_fork` with the block's residual add done by the native
     LayerNorm kernel (it reads y and r and writes the sum) instead of the producing GEMM's
-    epilogue."""
+    epilogue. ``scale`` (fp32 ``[B]``, one row of :func:`drop_path_scales`' table): stochastic
+    depth -- the sum is ``r + scale[b] * y`` for sample ``b``, the leading dimension, each sample
+    spanning ``rows_per_sample`` rows (default: all of a sample's rows); a sample whose scale is 0
+    takes ``r`` itself."""
+    if scale is not None:
+        rows = y.numel() // y.shape[-1]
+        if rows_per_sample is None:
+            rows_per_sample = rows // max(scale.numel(), 1)
+        if scale.dim() != 1 or y.shape[0] != scale.numel() or scale.numel() * rows_per_sample != rows:
+            raise ValueError(f"ln_add_fork: scale {tuple(scale.shape)} x {rows_per_sample} rows per sample does not "
+                             f"cover y {tuple(y.shape)}")
     if _use_native(y):
         from . import native_ops
-        return native_ops.ln_add_fork(y, r, ln, fp8_for, grad_fp8_for)
-    s = y + r
+        if scale is None:
+            return native_ops.ln_add_fork(y, r, ln, fp8_for, grad_fp8_for)
+        return native_ops.ln_add_fork(y, r, ln, fp8_for, grad_fp8_for, scale, rows_per_sample)
+    if scale is None:
+        s = y + r
+    else:
+        from .drop_path import scaled_add
+        s = scaled_add(y, r, scale)
     return s, ln(s)
+
+
+def drop_path_scales(state, p, inv_keep, batch: int, rank: int = 0):
+    """Stochastic depth's per-sample branch scales for one training forward: fp32
+    ``[len(p), batch]``, entry ``(j, b)`` 0 or ``inv_keep[j]``, a pure function of ``state`` =
+    ``[seed, step]`` (int32, on the model's device), the branch and the global sample index
+    ``rank * batch + b`` (``ops/drop_path.py``). ``state[1]`` advances by one. Native: one fill
+    launch and a one-thread tick on the device, no host sync (a replayed HIP graph advances the
+    counter too); torch path: the same table from the torch mirror (reads ``state`` on the host)."""
+    if _use_native(state):
+        from . import native_ops
+        return native_ops.drop_path_scales(state, p, inv_keep, batch, rank)
+    from .drop_path import drop_path_table
+    seed, step = (int(v) for v in state.tolist())
+    table = drop_path_table(seed, step, p, inv_keep, batch, rank, device=state.device)
+    with torch.no_grad():
+        state[1] = ((step + 1) & 0xFFFFFFFF) - (1 << 32 if (step + 1) & 0x80000000 else 0)
+    return table
 
 
 def attention(q, k, v):

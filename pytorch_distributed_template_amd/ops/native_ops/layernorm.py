@@ -181,14 +181,128 @@ class _LNAddFork(torch.autograd.Function):
         return dx, dx, dg, db, None, None, None, None, None
 
 
-def ln_add_fork(y, r, ln, fp8_for=None, grad_fp8_for=None):
+class _LNAddDropFork(torch.autograd.Function):
+    """_LNAddFork under stochastic depth: s = r + scale[b] * y for sample b (``rps`` rows each),
+    scale[b] 0 or 1/keep. A dropped sample's rows of y are not read and s holds r there. Backward:
+    r receives the summed gradient dx as in _LNAddFork, y receives dyb = scale[b] * dx (+0 where
+    dropped) written by the same kernel, and the e5m2 codes / bias gradient of the layer that
+    produced y (``_pdt_f8g`` / ``_pdt_db``) are formed from dyb and ride on it."""
+
+    @staticmethod
+    def forward(ctx, y, r, g, b, eps, f8meta, f8box, grad_owner, codes_only, scale, rps):
+        ctx.refs = (g, b)
+        shp = y.shape
+        D = shp[-1]
+        y2 = y.reshape(-1, D).contiguous()
+        r2 = r.reshape(-1, D).to(torch.bfloat16).contiguous()
+        rows = y2.shape[0]
+        sc = scale.detach().float().contiguous()
+        assert sc.numel() * rps == rows and sc.device == y.device, (tuple(sc.shape), rps, rows)
+        xs = torch.empty_like(y2)
+        h = torch.empty_like(y2)
+        stats = torch.empty((2, rows), dtype=torch.float32, device=y.device)
+        gf, bf = g.float().contiguous(), b.float().contiguous()
+        lib = _load()
+        if f8meta is not None:
+            q = torch.empty((rows, D), dtype=torch.uint8, device=y.device)
+            part = torch.empty(lib.pdt_ln_fwd_f8_blocks(rows) + 1, dtype=torch.float32, device=y.device)
+            dq = part[-1:]
+            _chk(lib.pdt_ln_add_dp_fwd(_p(y2), _p(r2), _p(xs), _p(gf), _p(bf), None if codes_only else _p(h),
+                                       _p(stats[0]), _p(stats[1]), rows, D, float(eps), _p(q), _p(f8meta), _p(part),
+                                       _p(dq), _p(sc), rps, _s()), "ln_add_dp_fwd_f8")
+            f8box.append((q, dq))
+        else:
+            _chk(lib.pdt_ln_add_dp_fwd(_p(y2), _p(r2), _p(xs), _p(gf), _p(bf), _p(h), _p(stats[0]), _p(stats[1]), rows,
+                                       D, float(eps), None, None, None, None, _p(sc), rps, _s()), "ln_add_dp_fwd")
+        ctx.save_for_backward(xs, gf, stats, sc)
+        ctx.shp = shp
+        ctx.grad_owner = grad_owner
+        ctx.rps = rps
+        return xs.reshape(shp), h.reshape(shp)
+
+    @staticmethod
+    def backward(ctx, g_res, dy):
+        none = (None,) * 7
+        if dy is None:  # the normalised output fed nothing: only the add's gradients
+            sc = ctx.saved_tensors[3].repeat_interleave(ctx.rps).reshape(*ctx.shp[:-1], 1)
+            gy = torch.where(sc != 0, g_res.float() * sc, torch.zeros((), device=sc.device)).to(g_res.dtype)
+            return (gy, g_res, None, None) + none
+        dyb, dx, dg, db = _ln_drop_backward(ctx, g_res, dy)
+        return (dyb, dx, dg, db) + none
+
+
+def _ln_drop_backward(ctx, g_res, dy):
+    """:func:`_ln_fork_backward` for _LNAddDropFork: (dyb, dx, dgamma, dbeta), the fp8 side
+    outputs taken from dyb and riding on it."""
+    x2, gf, stats, sc = ctx.saved_tensors
+    rows, D = x2.shape
+    lib = _load()
+    dev = x2.device
+    dy2 = dy.reshape(rows, D).to(torch.bfloat16).contiguous()
+    add = g_res.reshape(rows, D).to(torch.bfloat16).contiguous() if g_res is not None else None
+    dx = torch.empty_like(x2)
+    dyb = torch.empty_like(x2)
+    blocks = lib.pdt_ln_bwd_blocks(rows)
+    part = torch.empty(2 * blocks * D, dtype=torch.float32, device=dev)
+    dg, db = _grad_buf(ctx.refs[0], (D,)), _grad_buf(ctx.refs[1], (D,))
+    owner = ctx.grad_owner
+    gmeta = getattr(owner, "_pdt_fp8_gmeta", None) if owner is not None else None
+    codes = qpart = dq = cpart = pdb = None
+    if gmeta is not None and fp8_settings()["scaling"] == "delayed":
+        codes = torch.empty((rows, D), dtype=torch.uint8, device=dev)
+        qpart = torch.empty(blocks + 1, dtype=torch.float32, device=dev)
+        dq = qpart[-1:]
+        bias = getattr(owner, "bias", None)
+        if bias is not None and bias.requires_grad and os.environ.get("PDT_LN_DB", "1") == "1":
+            pdb = _grad_buf(bias, (D,))
+            cpart = torch.empty(blocks * D + lib.pdt_reduce_rows_work(blocks, D), dtype=torch.float32, device=dev)
+    else:
+        gmeta = None
+    _chk(lib.pdt_ln_dp_bwd(_p(dy2), _p(x2), _p(gf), _p(stats[0]), _p(stats[1]), _p(dx), _p(dyb), _p(dg), _p(db),
+                           _p(part), rows, D, 0, _p(add), _p(sc), ctx.rps, _p(codes), _p(gmeta), _p(qpart), _p(dq),
+                           _p(cpart), _p(pdb), 0, _s()), "ln_dp_bwd")
+    out = dyb.reshape(ctx.shp)
+    if codes is not None:
+        out._pdt_f8g = (codes, dq, owner)
+        if pdb is not None:
+            out._pdt_db = (pdb, owner)
+    return out, dx.reshape(ctx.shp), dg, db
+
+
+def ln_add_fork(y, r, ln, fp8_for=None, grad_fp8_for=None, scale=None, rows_per_sample=None):
     """(y + r, ln(y + r)) -- :func:`ln_fork` with the residual add done by the LayerNorm kernel
-    (``grad_fp8_for``: the fp8 layer that produced ``y``)."""
+    (``grad_fp8_for``: the fp8 layer that produced ``y``). ``scale`` (fp32 [samples], each 0 or
+    1/keep) with ``rows_per_sample``: stochastic depth, the sum is r + scale[sample] * y, formed
+    by the kernel's drop-path instantiation (see _LNAddDropFork)."""
     D = ln.normalized_shape[-1]
     if (len(ln.normalized_shape) != 1 or D not in (256, 512, 768, 1024) or not ln.elementwise_affine
             or y.dtype != torch.bfloat16 or r.shape != y.shape):
+        if scale is not None:
+            fallback("ln_add_fork", f"normalized_shape {tuple(ln.normalized_shape)}, {y.dtype} with a drop-path "
+                                    "scale (kernels: D in 256/512/768/1024, affine, bf16)")
+            from ..drop_path import scaled_add
+            return ln_fork(scaled_add(y, r, scale), ln, fp8_for, grad_fp8_for)
         return ln_fork(y + r.to(y.dtype), ln, fp8_for, grad_fp8_for)
+    if scale is not None:
+        rows = y.numel() // D
+        rps = rows // scale.numel() if rows_per_sample is None else int(rows_per_sample)
+        if scale.numel() * rps != rows:
+            raise ValueError(f"ln_add_fork: {scale.numel()} scales x {rps} rows per sample != {rows} rows")
+        return _apply_fork(_LNAddDropFork, (y, r), ln, fp8_for, grad_fp8_for, (scale, rps))
     return _apply_fork(_LNAddFork, (y, r), ln, fp8_for, grad_fp8_for)
+
+
+def drop_path_scales(state, p, inv_keep, batch, rank=0):
+    """The drop-path scale table [len(p), batch] (fp32) of this forward, filled on the device from
+    ``state`` = [seed, step] (int32), which then advances by one (csrc/drop_path.hip)."""
+    n = p.numel()
+    assert state.dtype == torch.int32 and state.numel() == 2 and state.is_contiguous()
+    assert p.dtype == torch.float32 and inv_keep.dtype == torch.float32 and inv_keep.numel() == n
+    assert p.is_contiguous() and inv_keep.is_contiguous() and p.device == state.device == inv_keep.device
+    table = torch.empty((n, int(batch)), dtype=torch.float32, device=state.device)
+    _chk(_load().pdt_drop_path_scales(_p(table), _p(state), _p(p), _p(inv_keep), n, int(batch),
+                                      int(rank) * int(batch), _s()), "drop_path_scales")
+    return table
 
 
 def ln_fork(x, ln, fp8_for=None, grad_fp8_for=None):
@@ -208,10 +322,11 @@ def ln_fork(x, ln, fp8_for=None, grad_fp8_for=None):
     return _apply_fork(_LNFork, (x,), ln, fp8_for, grad_fp8_for)
 
 
-def _apply_fork(fn, tensors, ln, fp8_for, grad_fp8_for):
-    """``fn`` (``_LNFork`` / ``_LNAddFork``) on its leading ``tensors`` with the fp8 side outputs
-    :func:`ln_fork` describes resolved: the returned LayerNorm output carries its e4m3 codes
-    (``_pdt_f8``, and ``_pdt_f8_only`` when its bf16 values were not written)."""
+def _apply_fork(fn, tensors, ln, fp8_for, grad_fp8_for, extra=()):
+    """``fn`` (``_LNFork`` / ``_LNAddFork`` / ``_LNAddDropFork``) on its leading ``tensors`` (and
+    trailing ``extra`` arguments) with the fp8 side outputs :func:`ln_fork` describes resolved: the
+    returned LayerNorm output carries its e4m3 codes (``_pdt_f8``, and ``_pdt_f8_only`` when its
+    bf16 values were not written)."""
     meta = None
     if fp8_for is not None and fp8_settings()["scaling"] == "delayed" and ln.normalized_shape[-1] % 128 == 0:
         meta = getattr(fp8_for, "_pdt_fp8_meta", None)
@@ -219,7 +334,7 @@ def _apply_fork(fn, tensors, ln, fp8_for, grad_fp8_for):
     if os.environ.get("PDT_FP8_LN_GRAD", "1") == "0":
         grad_fp8_for = None
     only = meta is not None and _ln_codes_only(fp8_for)
-    xo, h = fn.apply(*tensors, ln.weight, ln.bias, ln.eps, meta, box, grad_fp8_for, only)
+    xo, h = fn.apply(*tensors, ln.weight, ln.bias, ln.eps, meta, box, grad_fp8_for, only, *extra)
     if box:
         h._pdt_f8 = (box[0][0], box[0][1], fp8_for)
         if only:

@@ -14,6 +14,7 @@ flt = sys.argv[2] if len(sys.argv) > 2 else ""
 for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^; Occupancy: (\d+)", s, re.M | re.S):
     name, body, occ = m.group(1), m.group(2), m.group(3)
     v = re.search(r"; NumVgprs: (\d+)", body)
+    sg = re.search(r"; TotalNumSgprs: (\d+)", body)
     sp = re.search(r"; ScratchSize: (\d+)", body)
     lds = re.search(r"; LDSByteSize: (\d+)", body)
     try:
@@ -21,5 +22,5 @@ for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^; Occupancy: (\d+)", s, re.M | re.
     except Exception:
         dn = name
     if flt in dn:
-        print(f"vgpr={v.group(1) if v else '?':>4s} occ={occ} scratch={sp.group(1) if sp else '?'} "
+        print(f"vgpr={v.group(1) if v else '?':>4s} sgpr={sg.group(1) if sg else '?':>3s} occ={occ} scratch={sp.group(1) if sp else '?'} "
               f"lds={lds.group(1) if lds else '?'}  {dn[:110]}")
