@@ -18,13 +18,28 @@
 // pixels of one row and writes them with one 16-byte store (8 bytes for the odd-S row tail).
 // Every tap is one unaligned dword load covering the pixel's three bytes; edge taps use
 // clamped indices, never a branch around a load.
+//
+// Random Erasing (the ERASE instantiations): output b carries R rectangles (y0, x0, y1, x1),
+// half-open, in output coordinates, and a 32-bit noise key. A pixel inside any of them loads no
+// taps; its three channels are +0 (mode 0, "const") or N(0, 1) draws (mode 1, "pixel"), and the
+// pad channel stays +0. Every other pixel is the one the non-erase kernels produce, bit for bit.
+// The draw of pixel (oy, ox), channel c in 0..2, all hashing in uint32 with hash32 the mixer of
+// misc.hip:
+//   kq = hash32(ekey[b] ^ (oy S + ox) * 0x9E3779B9)
+//   h1 = hash32(kq ^ (2c + 1) * 0x85EBCA6B),  h2 = hash32(kq ^ (2c + 2) * 0x85EBCA6B)
+//   u1 = ((h1 >> 8) + 1) / 2^24  in (0, 1],   t = (h2 >> 8) / 2^23 = 2 u2  in [0, 2)
+//   z  = sqrtf(-2 logf(u1)) * cospif(t)       (Box-Muller; u1, t and -2 logf exact or one rounding)
+// so |z| <= sqrt(48 ln 2) = 5.77 and no inf or NaN arises; z is rounded once, to bf16. logf, sqrtf
+// and cospif are the accurate library functions (not __logf / __cosf): the argument of cospif is
+// exact, so no range-reduction error enters, and the erased pixels are the minority path.
 #include "pdt_common.h"
 
 namespace {
 constexpr int NT = 256;
 
 // One axis of the bilinear sampler: output coordinate o of n source pixels resized to S.
-// S2 = 2S, inv2S = 1 / 2S. (2S+1) n < 2^31 is checked on the host.
+// S2 = 2S, inv2S = 1 / 2S. (2S+1) n < 2^31 is checked on the host. (axis_taps_om below is its
+// twin for the erase paths: keep the two in step.)
 __device__ __forceinline__ void axis_taps(int o, int n, int S, int S2, float inv2S, int& i0, int& i1, float& l) {
   int num = (2 * o + 1) * n - S;
   num = num < 0 ? 0 : num;
@@ -152,6 +167,117 @@ __device__ __forceinline__ void store_pair(u16* __restrict__ out, long pix, bool
   }
 }
 
+// Random Erasing operands of output b (ERASE kernels): erect int32 [B][R][4], ekey uint32 [B],
+// mode 0 = const / 1 = pixel.
+struct EraseArgs {
+  const int* erect;
+  const uint32_t* ekey;
+  int R, mode;
+};
+struct MixEraseArgs : MixArgs {
+  EraseArgs er;
+};
+
+__device__ __forceinline__ uint32_t hash32(uint32_t x) {
+  x ^= x >> 16; x *= 0x7feb352dU;
+  x ^= x >> 15; x *= 0x846ca68bU;
+  x ^= x >> 16;
+  return x;
+}
+
+// The fill of erased pixel q = oy S + ox (the formula in the file header); mode is wave-uniform.
+__device__ __forceinline__ PixelOut erase_fill(uint32_t key, uint32_t q, int mode) {
+  if (!mode) return PixelOut{0u, 0u};
+  const uint32_t kq = hash32(key ^ q * 0x9E3779B9u);
+  float z[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const uint32_t h1 = hash32(kq ^ (uint32_t)(2 * c + 1) * 0x85EBCA6Bu);
+    const uint32_t h2 = hash32(kq ^ (uint32_t)(2 * c + 2) * 0x85EBCA6Bu);
+    const float u1 = (float)((h1 >> 8) + 1u) * (1.f / 16777216.f);
+    const float t = (float)(h2 >> 8) * (1.f / 8388608.f);
+    z[c] = sqrtf(-2.f * logf(u1)) * cospif(t);
+  }
+  return PixelOut{pack2bf(z[0], z[1]), pack2bf(z[2], 0.f)};
+}
+
+// The erase paths sample under a per-lane branch, and must still give the bits of the straight-line
+// paths. There the compiler contracts the blend weight l = r * inv2S into 1 - l, i.e. forms
+// fma(-inv2S, r, 1) with one rounding (every 1 - l of the non-erase kernels' ISA is that v_fma);
+// across a branch it would round l first. So these twins of axis_taps / view_taps / blend_taps
+// spell that fma out and carry 1 - l beside l.
+struct TapsOm {
+  Taps t;          // p00..p11 as loaded: blend_taps_om shifts them, behind the caller's pin
+  float omy, omx;  // 1 - ly, 1 - lx
+  uint32_t sh;     // load_rgb's four shifts (0 or 8), one per byte
+};
+
+__device__ __forceinline__ void axis_taps_om(int o, int n, int S, int S2, float inv2S, int& i0, int& i1, float& l,
+                                             float& om) {
+  int num = (2 * o + 1) * n - S;
+  num = num < 0 ? 0 : num;
+  int i = (int)((float)num * inv2S);
+  int r = num - i * S2;
+  if (r < 0) { --i; r += S2; }
+  if (r >= S2) { ++i; r -= S2; }
+  l = (float)r * inv2S;
+  om = fmaf(-inv2S, (float)r, 1.f);
+  i0 = i < n - 1 ? i : n - 1;
+  i1 = i0 + 1 < n - 1 ? i0 + 1 : n - 1;
+}
+
+// load_rgb without its shift: inside a branch the shift would wait for the load there, and the
+// other pixel's loads would issue behind that wait
+__device__ __forceinline__ uint32_t load_rgb_raw(const uint8_t* __restrict__ img, uint32_t off, uint32_t& sh) {
+  const uint32_t back = off > 0 ? 1u : 0u;
+  uint32_t w;
+  __builtin_memcpy(&w, img + (off - back), 4);
+  sh = back * 8;
+  return w;
+}
+
+// view_taps for a lane that samples (on); any other lane issues no load
+__device__ __forceinline__ TapsOm view_taps_om(bool on, const View& v, int oy, int ox, int Ws, int S, int S2,
+                                               float inv2S) {
+  TapsOm r{};
+  if (on) {
+    int iy, iy1, ix, ix1;
+    axis_taps_om(oy, v.h, S, S2, inv2S, iy, iy1, r.t.ly, r.omy);
+    axis_taps_om(v.flip ? S - 1 - ox : ox, v.w, S, S2, inv2S, ix, ix1, r.t.lx, r.omx);
+    const uint32_t row0 = (uint32_t)((v.y0 + iy) * Ws + v.x0), row1 = (uint32_t)((v.y0 + iy1) * Ws + v.x0);
+    uint32_t s00, s01, s10, s11;
+    r.t.p00 = load_rgb_raw(v.img, (row0 + (uint32_t)ix) * 3u, s00);
+    r.t.p01 = load_rgb_raw(v.img, (row0 + (uint32_t)ix1) * 3u, s01);
+    r.t.p10 = load_rgb_raw(v.img, (row1 + (uint32_t)ix) * 3u, s10);
+    r.t.p11 = load_rgb_raw(v.img, (row1 + (uint32_t)ix1) * 3u, s11);
+    r.sh = s00 | (s01 << 8) | (s10 << 16) | (s11 << 24);
+  }
+  return r;
+}
+
+__device__ __forceinline__ Rgb blend_taps_om(const TapsOm& q) {
+  const Taps& t = q.t;
+  const uint32_t p00 = t.p00 >> (q.sh & 0xffu), p01 = t.p01 >> ((q.sh >> 8) & 0xffu);
+  const uint32_t p10 = t.p10 >> ((q.sh >> 16) & 0xffu), p11 = t.p11 >> (q.sh >> 24);
+  const float w00 = q.omy * q.omx, w01 = q.omy * t.lx, w10 = t.ly * q.omx, w11 = t.ly * t.lx;
+  Rgb r;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float a = (float)((p00 >> (8 * c)) & 0xffu), b = (float)((p01 >> (8 * c)) & 0xffu);
+    const float d = (float)((p10 >> (8 * c)) & 0xffu), e = (float)((p11 >> (8 * c)) & 0xffu);
+    r.v[c] = fmaf(w11, e, fmaf(w10, d, fmaf(w01, b, w00 * a)));
+  }
+  return r;
+}
+
+// Mixup of one pixel on the fp32 0..255 values: the partner's inside the rectangle
+__device__ __forceinline__ Rgb mixup_rgb(const Rgb& own, const Rgb& par, bool in, float wo, float wp) {
+  Rgb r;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) r.v[c] = in ? par.v[c] : fmaf(wo, own.v[c], wp * par.v[c]);
+  return r;
+}
+
 // grid.x = B * nblk: workgroup (b, k) covers pixel pairs [k NT, (k+1) NT) of image b's S * P
 // pairs (P = ceil(S / 2) pairs per output row).
 //
@@ -163,7 +289,12 @@ __device__ __forceinline__ void store_pair(u16* __restrict__ out, long pix, bool
 //   * nothing to mix (w_own == 1, empty rectangle): the plain path, instruction for instruction;
 //   * CutMix (w_own == 1): each pixel selects its view -- image base and box -- and samples once;
 //   * Mixup: both pixels' taps of both views are in flight together, then the blend.
-template <bool MIX, class Mix>
+//
+// ERASE: the R rectangles of image b are wave-uniform (scalar loads). All empty: fall through to
+// the code above and below, as the non-erase instantiation runs it. Otherwise the rectangle test
+// is per lane and per pixel; an erased pixel (and the dropped second pixel of the odd-S tail)
+// issues no load, every other pixel samples as its mixing case says, one view_taps_om per pixel.
+template <bool MIX, bool ERASE, class Mix>
 __global__ void __launch_bounds__(NT)
 crop_resize_norm_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ idx, const int* __restrict__ box,
                         u16* __restrict__ out, long img_bytes, int Ws, int S, int P, uint32_t nblk, FastDiv dP,
@@ -181,6 +312,78 @@ crop_resize_norm_kernel(const uint8_t* __restrict__ src, const int64_t* __restri
   const bool pair = ox0 + 1 < S;
   const int ox1 = pair ? ox0 + 1 : ox0;  // odd-S tail: the second pixel is computed and dropped
   const int S2 = 2 * S;
+
+  if constexpr (ERASE) {
+    const EraseArgs* era;
+    if constexpr (MIX) era = &mix.er; else era = &mix;
+    const int R = era->R;
+    const int* er = era->erect + (long)b * R * 4;
+    // all eight slots at once, the ones past R reading rectangle R - 1 again: no loop, so these
+    // scalar loads issue beside the box's and the decision costs one round trip, not one per slot
+    bool any = false;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const int* e = er + 4 * min(r, R - 1);
+      const int ey0 = e[0], ex0 = e[1], ey1 = e[2], ex1 = e[3];
+      any |= (ey0 < ey1) & (ex0 < ex1);
+    }
+    if (any) {
+      bool ea = false, ec = false;
+      for (int r = 0; r < R; ++r) {
+        const int ey0 = er[4 * r], ex0 = er[4 * r + 1], ey1 = er[4 * r + 2], ex1 = er[4 * r + 3];
+        const bool iny = oy >= ey0 && oy < ey1;
+        ea |= iny && ox0 >= ex0 && ox0 < ex1;
+        ec |= iny && ox1 >= ex0 && ox1 < ex1;
+      }
+      const uint32_t key = era->ekey[b];
+      const int mode = era->mode;
+      const uint32_t q = (uint32_t)(oy * S + ox0);
+      const bool sa = !ea, sc = pair && !ec;  // the pixels that sample
+      const long pix = ((long)b * S + oy) * S + ox0;
+      const View own{img, y0, x0, h, w, flip};
+      PixelOut a{0u, 0u}, c{0u, 0u};
+      bool mixup = false;
+      View va = own, vc = own;
+      if constexpr (MIX) {
+        const int* rc = mix.rect + (long)b * 4;
+        const int ry0 = rc[0], rx0 = rc[1], ry1 = rc[2], rx1 = rc[3];
+        const float wo = mix.w_own[b];
+        const int* pb = mix.pbox + (long)b * 5;
+        const View par{src + (long)mix.pidx[b] * img_bytes, pb[0], pb[1], pb[2], pb[3], pb[4]};
+        const bool iny = oy >= ry0 && oy < ry1;
+        const bool ina = iny && ox0 >= rx0 && ox0 < rx1, inc = iny && ox1 >= rx0 && ox1 < rx1;
+        mixup = wo != 1.f;
+        if (mixup) {
+          TapsOm oa = view_taps_om(sa, own, oy, ox0, Ws, S, S2, inv2S), oc = view_taps_om(sc, own, oy, ox1, Ws, S, S2, inv2S);
+          TapsOm qa = view_taps_om(sa, par, oy, ox0, Ws, S, S2, inv2S), qc = view_taps_om(sc, par, oy, ox1, Ws, S, S2, inv2S);
+          asm volatile("" : "+v"(oa.t.p00), "+v"(oa.t.p01), "+v"(oa.t.p10), "+v"(oa.t.p11), "+v"(oc.t.p00),
+                            "+v"(oc.t.p01), "+v"(oc.t.p10), "+v"(oc.t.p11), "+v"(qa.t.p00), "+v"(qa.t.p01),
+                            "+v"(qa.t.p10), "+v"(qa.t.p11), "+v"(qc.t.p00), "+v"(qc.t.p01), "+v"(qc.t.p10),
+                            "+v"(qc.t.p11));
+          const float wp = 1.f - wo;
+          if (sa) a = finish(mixup_rgb(blend_taps_om(oa), blend_taps_om(qa), ina, wo, wp), m0, m1, m2, s0, s1, s2);
+          if (sc) c = finish(mixup_rgb(blend_taps_om(oc), blend_taps_om(qc), inc, wo, wp), m0, m1, m2, s0, s1, s2);
+        } else {
+          va = View{ina ? par.img : own.img, ina ? par.y0 : own.y0, ina ? par.x0 : own.x0,
+                    ina ? par.h : own.h,     ina ? par.w : own.w,   ina ? par.flip : own.flip};
+          vc = View{inc ? par.img : own.img, inc ? par.y0 : own.y0, inc ? par.x0 : own.x0,
+                    inc ? par.h : own.h,     inc ? par.w : own.w,   inc ? par.flip : own.flip};
+        }
+      }
+      if (!mixup) {
+        TapsOm ta = view_taps_om(sa, va, oy, ox0, Ws, S, S2, inv2S), tc = view_taps_om(sc, vc, oy, ox1, Ws, S, S2, inv2S);
+        // every load issued before the first use (the pins below, for the same reason)
+        asm volatile("" : "+v"(ta.t.p00), "+v"(ta.t.p01), "+v"(ta.t.p10), "+v"(ta.t.p11), "+v"(tc.t.p00),
+                          "+v"(tc.t.p01), "+v"(tc.t.p10), "+v"(tc.t.p11));
+        if (sa) a = finish(blend_taps_om(ta), m0, m1, m2, s0, s1, s2);
+        if (sc) c = finish(blend_taps_om(tc), m0, m1, m2, s0, s1, s2);
+      }
+      if (ea) a = erase_fill(key, q, mode);
+      if (pair && ec) c = erase_fill(key, q + 1u, mode);
+      store_pair(out, pix, pair, a, c);
+      return;
+    }
+  }
 
   if constexpr (MIX) {
     const int* rc = mix.rect + (long)b * 4;
@@ -251,7 +454,7 @@ crop_resize_norm_kernel(const uint8_t* __restrict__ src, const int64_t* __restri
   }
 }
 
-template <bool MIX, class Mix>
+template <bool MIX, bool ERASE, class Mix>
 int launch(const void* src, int Hs, int Ws, const int64_t* idx, const int* box, Mix mix, void* out, long B, int S,
            int Cp, const float* mean, const float* inv_std, hipStream_t st) {
   if (!src || !box || !out || !mean || !inv_std) return -1;
@@ -262,7 +465,7 @@ int launch(const void* src, int Hs, int Ws, const int64_t* idx, const int* box, 
   const int P = (S + 1) / 2;
   const long nblk = ((long)S * P + NT - 1) / NT;
   if (B * nblk > 0x7fffffffL) return -1;
-  hipLaunchKernelGGL((crop_resize_norm_kernel<MIX, Mix>), dim3((unsigned)(B * nblk)), dim3(NT), 0, st,
+  hipLaunchKernelGGL((crop_resize_norm_kernel<MIX, ERASE, Mix>), dim3((unsigned)(B * nblk)), dim3(NT), 0, st,
                      (const uint8_t*)src, idx, box, (u16*)out, img_bytes, Ws, S, P, (uint32_t)nblk,
                      make_fastdiv((uint32_t)P), 1.f / (float)(2 * S), mean[0], mean[1], mean[2], inv_std[0],
                      inv_std[1], inv_std[2], mix);
@@ -277,7 +480,7 @@ int launch(const void* src, int Hs, int Ws, const int64_t* idx, const int* box, 
 PDT_API int pdt_crop_resize_norm_u8_bf16(const void* src, int Hs, int Ws, const int64_t* idx, const int* box, void* out,
                                          long B, int S, int Cp, const float* mean, const float* inv_std,
                                          hipStream_t st) {
-  return launch<false>(src, Hs, Ws, idx, box, NoMix{}, out, B, S, Cp, mean, inv_std, st);
+  return launch<false, false>(src, Hs, Ws, idx, box, NoMix{}, out, B, S, Cp, mean, inv_std, st);
 }
 
 // The same with Mixup / CutMix (see the kernel): pidx int64 [B] the partner's source image, pbox
@@ -288,5 +491,25 @@ PDT_API int pdt_crop_resize_norm_mix_u8_bf16(const void* src, int Hs, int Ws, co
                                              const float* w_own, void* out, long B, int S, int Cp, const float* mean,
                                              const float* inv_std, hipStream_t st) {
   if (!pidx || !pbox || !rect || !w_own) return -1;
-  return launch<true>(src, Hs, Ws, idx, box, MixArgs{pidx, pbox, rect, w_own}, out, B, S, Cp, mean, inv_std, st);
+  return launch<true, false>(src, Hs, Ws, idx, box, MixArgs{pidx, pbox, rect, w_own}, out, B, S, Cp, mean, inv_std, st);
+}
+
+// Either of the two with Random Erasing (see the kernel). pidx, pbox, rect, w_own: all four null
+// (no mixing) or all four set (mixing, as above). erect int32 [B][R][4] = y0, x0, y1, x1 (half-open,
+// inside [0, S]^2; empty when y0 == y1 or x0 == x1), R in 1..8; ekey uint32 [B], the noise key of
+// each output; emode 0 = const (+0), 1 = pixel (N(0, 1) per element). On the device and trusted
+// like the boxes (data/packed.py: validate_erase).
+PDT_API int pdt_crop_resize_norm_erase_u8_bf16(const void* src, int Hs, int Ws, const int64_t* idx, const int* box,
+                                               const int64_t* pidx, const int* pbox, const int* rect,
+                                               const float* w_own, const int* erect, int R, const void* ekey,
+                                               int emode, void* out, long B, int S, int Cp, const float* mean,
+                                               const float* inv_std, hipStream_t st) {
+  const int nmix = (pidx != nullptr) + (pbox != nullptr) + (rect != nullptr) + (w_own != nullptr);
+  if (nmix != 0 && nmix != 4) return -1;
+  if (!erect || !ekey || R < 1 || R > 8 || (emode != 0 && emode != 1)) return -1;
+  const EraseArgs er{erect, (const uint32_t*)ekey, R, emode};
+  if (nmix == 0) return launch<false, true>(src, Hs, Ws, idx, box, er, out, B, S, Cp, mean, inv_std, st);
+  MixEraseArgs me;
+  me.pidx = pidx, me.pbox = pbox, me.rect = rect, me.w_own = w_own, me.er = er;
+  return launch<true, true>(src, Hs, Ws, idx, box, me, out, B, S, Cp, mean, inv_std, st);
 }

@@ -202,6 +202,11 @@ PDT_API int pdt_crop_resize_norm_mix_u8_bf16(const void* src, int Hs, int Ws, co
                                              const int64_t* pidx, const int* pbox, const int* rect,
                                              const float* w_own, void* out, long B, int S, int Cp, const float* mean,
                                              const float* inv_std, hipStream_t st);
+PDT_API int pdt_crop_resize_norm_erase_u8_bf16(const void* src, int Hs, int Ws, const int64_t* idx, const int* box,
+                                               const int64_t* pidx, const int* pbox, const int* rect,
+                                               const float* w_own, const int* erect, int R, const void* ekey,
+                                               int emode, void* out, long B, int S, int Cp, const float* mean,
+                                               const float* inv_std, hipStream_t st);
 
 // layernorm.hip
 PDT_API int pdt_ln_fwd(const void* x, const float* g, const float* b, void* y, float* mean, float* rstd, int rows,

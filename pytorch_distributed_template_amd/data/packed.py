@@ -43,6 +43,23 @@ construction, and the draws (:func:`mix_params`) are keyed by ``(seed, epoch, fi
 sample index of the batch)`` -- reproducible and independent of which thread computes them, but
 not of batch size or world size. Nobody has trained a model to convergence with this recipe
 here; what is tested is that the mixed batch and the loss are the ones the parameters describe.
+
+**Random Erasing** (``re_prob``, ``re_mode``, ``re_count``, ``re_area``, ``re_aspect``; off by
+default, training only) follows timm's ``RandomErasing``: with probability ``re_prob`` a sample
+gets ``re_count`` rectangles (:func:`random_erasing_rects`), and every output element inside one
+is replaced -- by an independent N(0, 1) draw in normalized space (``"pixel"``) or by +0
+(``"const"``). It comes last, after Mixup / CutMix, and leaves the target alone. It is a decision
+at the kernel's final store in the same launch (the ERASE instantiations of
+``csrc/image_aug.hip``): an erased pixel loads no taps, and there is no pass over the batch
+afterwards. Like the crop boxes, rectangles and fill are counter-based -- a pure function of
+``(seed, epoch, global sample index)`` and, for the fill, ``(oy, ox, channel)``, from a hash
+stream salted apart from the crop-box draws -- so they do not depend on batch size, world size,
+position in the batch or loader mode, and switching erasing on changes no crop box, flip or mix
+parameter. With ``re_prob = 0`` the loader runs the uploads and entry points it runs without the
+arguments. Untrained here, like the rest of the recipe. Two helpers beside the functions the
+loader calls: :func:`u32_bits` (the int32 bit pattern of uint32 values carried in int64, as the
+kernel reads the keys) and :func:`erase_noise` (the kernel's draws in float64, which
+:func:`erase_images_torch` rounds to fp32).
 """
 from __future__ import annotations
 
@@ -330,6 +347,131 @@ def mix_images_torch(x, partner, w_own, rect):
     return torch.where(inside[:, None], xp, out)
 
 
+# ----------------------------------------------------------------------------- erasing
+_ERASE_MODES = ("pixel", "const")
+_ERASE_SALT = 0x45524153  # "ERAS": the erase stream of a sample is keyed apart from its crop-box stream
+_RE_AREA = (0.02, 1 / 3)
+_RE_ASPECT = (0.3, 1 / 0.3)
+
+
+def check_erase_args(re_prob, re_mode, re_count, re_area, re_aspect):
+    """Raise ValueError on a probability outside [0, 1], an unknown mode, ``re_count`` outside 1..8,
+    a non-positive or reversed area or aspect range, or an area maximum above 1."""
+    if not (0.0 <= float(re_prob) <= 1.0):
+        raise ValueError(f"re_prob must lie in [0, 1], got {re_prob!r}")
+    if re_mode not in _ERASE_MODES:
+        raise ValueError(f"re_mode must be one of {_ERASE_MODES}, got {re_mode!r}")
+    if isinstance(re_count, bool) or not isinstance(re_count, (int, np.integer)) or not (1 <= int(re_count) <= 8):
+        raise ValueError(f"re_count must be an integer in 1..8, got {re_count!r}")
+    for name, v in (("re_area", re_area), ("re_aspect", re_aspect)):
+        if len(v) != 2 or not (0.0 < float(v[0]) <= float(v[1])) or math.isinf(float(v[1])):
+            raise ValueError(f"{name} must be a (min, max) pair with 0 < min <= max, got {v!r}")
+    if float(re_area[1]) > 1.0:
+        raise ValueError(f"re_area's maximum must be at most 1 (a fraction of the output), got {re_area!r}")
+
+
+def _erase_state(indices, epoch, seed) -> torch.Tensor:
+    """uint32 (in int64) [B]: the erase stream's state of each sample -- the crop-box stream's
+    state of :func:`_uniforms`, hashed once more with a salt."""
+    idx = torch.as_tensor(indices, dtype=torch.int64).reshape(-1)
+    s = _hash32(((idx & _M32) * 0x9E3779B9 & _M32) ^ (int(seed) & _M32))
+    s = _hash32(s ^ ((int(epoch) & _M32) * 0x85EBCA6B & _M32) ^ ((idx >> 32) & _M32))
+    return _hash32(s ^ _ERASE_SALT)
+
+
+def erase_keys(indices, epoch, seed) -> torch.Tensor:
+    """The noise key of each global sample in ``indices``: uint32 values in int64 [B] (draw 0 of
+    the sample's erase stream; the rectangles use draws 1...). A pure function of ``(seed, epoch,
+    index)``."""
+    return _hash32(_erase_state(indices, epoch, seed))
+
+
+def random_erasing_rects(indices, epoch, seed, S, re_prob=0.25, re_count=1, re_area=_RE_AREA,
+                         re_aspect=_RE_ASPECT) -> torch.Tensor:
+    """int32 [B, re_count, 4] = (y0, x0, y1, x1), half-open, in the ``S x S`` output: timm's
+    ``RandomErasing`` boxes of global sample ``indices``. With probability ``1 - re_prob`` a sample
+    has no rectangle; otherwise each of its ``re_count`` rectangles makes up to 10 tries of area =
+    ``S S U(re_area) / re_count`` and a log-uniform aspect ``r``, ``h = round(sqrt(area r))``,
+    ``w = round(sqrt(area / r))``, accepted when ``h < S`` and ``w < S``, then a uniform corner such
+    that it lies inside the output. A rectangle with no accepted try (or of no pixel) is all zeros.
+    Each row is a pure function of ``(seed, epoch, index)``: draw ``j`` of the sample's erase stream
+    is ``hash32(j * 0xC2B2AE35 ^ state)``, ``j = 1`` the decision, then (area, aspect, y, x) per try."""
+    check_erase_args(re_prob, "pixel", re_count, re_area, re_aspect)
+    S, R = int(S), int(re_count)
+    if S <= 0:
+        raise ValueError("random_erasing_rects needs S >= 1")
+    s = _erase_state(indices, epoch, seed)
+    B = s.shape[0]
+    j = torch.arange(1, 2 + 4 * _TRIES * R, dtype=torch.int64)
+    u = (_hash32(((j * 0xC2B2AE35) & _M32)[None, :] ^ s[:, None]) >> 8).to(torch.float64) / 16777216.0
+    erased = u[:, 0] < float(re_prob)
+    t = u[:, 1:].reshape(B, R, _TRIES, 4)
+    area = S * S * (float(re_area[0]) + t[..., 0] * (float(re_area[1]) - float(re_area[0]))) / R
+    lr0, lr1 = math.log(float(re_aspect[0])), math.log(float(re_aspect[1]))
+    ar = torch.exp(lr0 + t[..., 1] * (lr1 - lr0))
+    h = torch.round(torch.sqrt(area * ar)).to(torch.int64)
+    w = torch.round(torch.sqrt(area / ar)).to(torch.int64)
+    ok = (h < S) & (w < S)
+    first = torch.argmax(ok.to(torch.int64), dim=2, keepdim=True)  # first accepted try (0 when none is)
+    h, w = torch.gather(h, 2, first)[..., 0], torch.gather(w, 2, first)[..., 0]
+    y0 = torch.floor(torch.gather(t[..., 2], 2, first)[..., 0] * (S - h + 1)).to(torch.int64)
+    x0 = torch.floor(torch.gather(t[..., 3], 2, first)[..., 0] * (S - w + 1)).to(torch.int64)
+    keep = erased[:, None] & ok.any(dim=2) & (h > 0) & (w > 0)
+    rect = torch.stack([y0, x0, y0 + h, x0 + w], dim=2)
+    return torch.where(keep[..., None], rect, torch.zeros_like(rect)).to(torch.int32)
+
+
+def validate_erase(rects, S):
+    """Raise unless ``rects`` is int32 [B, R, 4] with R in 1..8 and every rectangle lies inside
+    ``[0, S]^2`` with ``y0 <= y1`` and ``x0 <= x1`` (the kernel trusts what it is given)."""
+    if rects.dim() != 3 or rects.shape[2] != 4 or not (1 <= rects.shape[1] <= 8):
+        raise ValueError(f"erase rectangles must be [B, 1..8, 4], got {tuple(rects.shape)}")
+    r = rects.to(torch.int64)
+    bad = ((r[..., 0] < 0) | (r[..., 1] < 0) | (r[..., 2] > S) | (r[..., 3] > S) | (r[..., 0] > r[..., 2])
+           | (r[..., 1] > r[..., 3]))
+    if bool(bad.any()):
+        i, k = (int(v) for v in torch.nonzero(bad)[0])
+        raise ValueError(f"erase rectangle {rects[i, k].tolist()} ({k}) of batch entry {i} is outside the "
+                         f"{S}x{S} output")
+
+
+def u32_bits(keys) -> torch.Tensor:
+    """int32 tensor with the bits of uint32 values carried in int64 (what the kernel reads)."""
+    k = torch.as_tensor(keys, dtype=torch.int64)
+    return torch.where(k >= 1 << 31, k - (1 << 32), k).to(torch.int32)
+
+
+def erase_noise(keys, pos, S):
+    """float64 N(0, 1) draws of the kernel's noise (``csrc/image_aug.hip``) at ``pos`` = int64
+    [n, 3] rows ``(b, oy, ox)``: [n, 3], one column per channel. ``keys``: uint32 in int64 [B]."""
+    kq = _hash32(keys.to(torch.int64)[pos[:, 0]] ^ (((pos[:, 1] * S + pos[:, 2]) & _M32) * 0x9E3779B9 & _M32))
+    c = torch.arange(3, dtype=torch.int64)
+    h1 = _hash32(kq[:, None] ^ ((2 * c + 1) * 0x85EBCA6B & _M32)[None, :])
+    h2 = _hash32(kq[:, None] ^ ((2 * c + 2) * 0x85EBCA6B & _M32)[None, :])
+    u1 = ((h1 >> 8) + 1).to(torch.float64) / 16777216.0
+    t = (h2 >> 8).to(torch.float64) / 8388608.0
+    return torch.sqrt(-2.0 * torch.log(u1)) * torch.cos(math.pi * t)
+
+
+def erase_images_torch(x, rects, keys, mode):
+    """The erase in torch on normalized fp32 views ``x`` [B, 3, S, S]: every element inside any of
+    the sample's rectangles becomes +0 (``"const"``) or the kernel's N(0, 1) draw for ``(keys[b],
+    oy, ox, channel)`` (``"pixel"``), formed in float64 and rounded to fp32."""
+    if mode not in _ERASE_MODES:
+        raise ValueError(f"re_mode must be one of {_ERASE_MODES}, got {mode!r}")
+    B, _, S, _ = x.shape
+    r = rects.to(torch.int64).view(B, -1, 1, 1, 4)
+    yy = torch.arange(S).view(1, 1, S, 1)
+    xx = torch.arange(S).view(1, 1, 1, S)
+    inside = ((yy >= r[..., 0]) & (yy < r[..., 2]) & (xx >= r[..., 1]) & (xx < r[..., 3])).any(dim=1)  # [B, S, S]
+    out = x.clone()
+    if mode == "const":
+        return out.masked_fill_(inside[:, None], 0.0)
+    pos = torch.nonzero(inside)
+    out.permute(0, 2, 3, 1)[inside] = erase_noise(keys, pos, S).to(x.dtype)
+    return out
+
+
 def crop_resize_normalize_torch(images, box, S, mean, std, dtype=torch.float32):
     """The kernel's math in torch: ``images`` uint8 [B, Hs, Ws, 3] -> [B, 3, S, S] ``dtype``
     (computed in fp32): per-sample crop, bilinear ``F.interpolate`` (``align_corners=False``, no
@@ -352,7 +494,8 @@ class PackedImageLoader:
 
     Yields ``(images [B, 3, S, S], labels int64 [B])`` on ``device`` -- with Mixup / CutMix
     switched on (``mixup_alpha`` / ``cutmix_alpha`` > 0 and ``training``), ``(images,
-    MixedTarget)``. On the native path
+    MixedTarget)``. Random Erasing (``re_prob`` > 0 and ``training``) changes pixels only, never
+    the target. On the native path
     (CUDA device, kernel library present, bf16, ``channels_last``) ``images`` is a view into
     bf16 ``[B, S, S, 4]`` tagged ``pdt_nhwc_pad = 4``; otherwise the torch path returns
     ``dtype`` (``channels_last`` strides when asked).
@@ -366,8 +509,9 @@ class PackedImageLoader:
                  scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), hflip=0.5, crop_fraction=0.875, mean=None, std=None,
                  resident="auto", resident_limit_gb=16, prefetch=2, dtype=None, channels_last=True, device=None,
                  num_workers=0, mixup_alpha=0.0, cutmix_alpha=0.0, mix_prob=1.0, mix_switch_prob=0.5,
-                 mix_mode="batch"):
+                 mix_mode="batch", re_prob=0.0, re_mode="pixel", re_count=1, re_area=_RE_AREA, re_aspect=_RE_ASPECT):
         check_mix_args(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, mix_mode)
+        check_erase_args(re_prob, re_mode, re_count, re_area, re_aspect)
         self.dataset = open_packed(data_dir)
         ds = self.dataset
         self.batch_size = int(batch_size)
@@ -380,6 +524,10 @@ class PackedImageLoader:
         self.mix_prob, self.mix_switch_prob, self.mix_mode = float(mix_prob), float(mix_switch_prob), mix_mode
         # samples are mixed in training only, and only when a method is switched on
         self.mixing = bool(training) and (self.mixup_alpha > 0 or self.cutmix_alpha > 0)
+        self.re_prob, self.re_mode, self.re_count = float(re_prob), re_mode, int(re_count)
+        self.re_area, self.re_aspect = tuple(float(v) for v in re_area), tuple(float(v) for v in re_aspect)
+        # samples are erased in training only
+        self.erasing = bool(training) and self.re_prob > 0
         self.mean = tuple(mean) if mean is not None else (ds.mean or IMAGENET_MEAN)
         self.std = tuple(std) if std is not None else (ds.std or IMAGENET_STD)
         assert len(self.mean) == 3 and len(self.std) == 3 and all(s > 0 for s in self.std)
@@ -454,6 +602,18 @@ class PackedImageLoader:
         validate_mix(*m, self.image_size)
         return m
 
+    def erase(self, indices, epoch=None):
+        """The validated Random Erasing parameters ``(rects, keys)`` (host: int32 [B, re_count, 4],
+        uint32 in int64 [B]) of global sample ``indices`` in ``epoch`` (default: the current one);
+        None when the loader does not erase."""
+        if not self.erasing:
+            return None
+        epoch = self.epoch if epoch is None else epoch
+        rects = random_erasing_rects(indices, epoch, self.seed, self.image_size, self.re_prob, self.re_count,
+                                     self.re_area, self.re_aspect)
+        validate_erase(rects, self.image_size)
+        return rects, erase_keys(indices, epoch, self.seed)
+
     def __iter__(self):
         if self.mode == "torch":
             return self._iter_torch()
@@ -473,66 +633,108 @@ class PackedImageLoader:
             imgs = np.empty((len(idx),) + ds.images.shape[1:], dtype=np.uint8)
             imgs[order] = ds.images[idx[order]]
             mix = self.mix(indices, epoch)
+            erase = self.erase(indices, epoch)
             y = torch.from_numpy(ds.labels[idx])
-            if mix is None:
+            if mix is None and erase is None:
                 x = crop_resize_normalize_torch(torch.from_numpy(imgs), box, self.image_size, self.mean, self.std,
                                                 self.dtype)
                 yield x.contiguous(memory_format=fmt).to(self.device), y.to(self.device)
                 continue
-            partner, w_own, rect, lam = mix
             x = crop_resize_normalize_torch(torch.from_numpy(imgs), box, self.image_size, self.mean, self.std)
-            x = mix_images_torch(x, partner, w_own, rect).to(self.dtype)  # blend and paste in fp32
-            target = MixedTarget(y.to(self.device), y[partner].to(self.device), lam.to(self.device))
-            yield x.contiguous(memory_format=fmt).to(self.device), target
+            target = y.to(self.device)
+            if mix is not None:
+                partner, w_own, rect, lam = mix
+                x = mix_images_torch(x, partner, w_own, rect)  # blend and paste in fp32
+                target = MixedTarget(target, y[partner].to(self.device), lam.to(self.device))
+            if erase is not None:
+                x = erase_images_torch(x, *erase, self.re_mode)  # last, as timm: the target does not change
+            yield x.to(self.dtype).contiguous(memory_format=fmt).to(self.device), target
 
     # ------------------------------------------------------------------ native paths
-    def _upload_params(self, kidx, labels, box):
+    @staticmethod
+    def _erase_words(erase, B):
+        """int32 words the erase parameters add to a batch's pinned buffer: the rectangles and one key
+        per sample, behind everything else (the int64 vectors stay in front, 8-byte aligned)."""
+        return 0 if erase is None else (4 * erase[0].shape[1] + 1) * B
+
+    @staticmethod
+    def _put_erase(host, off, erase):
+        """Write ``erase`` = (rects, keys) into the pinned words ``host[off:]``."""
+        rects, keys = erase
+        B, R = rects.shape[:2]
+        host[off:off + 4 * R * B].view(B, R, 4).copy_(rects)
+        host[off + 4 * R * B:off + (4 * R + 1) * B].copy_(u32_bits(keys))
+
+    @staticmethod
+    def _erase_views(dev, off, erase):
+        """The device views ``(erect, ekey)`` of what :meth:`_put_erase` wrote."""
+        B, R = erase[0].shape[:2]
+        return dev[off:off + 4 * R * B].view(B, R, 4), dev[off + 4 * R * B:off + (4 * R + 1) * B]
+
+    def _upload_params(self, kidx, labels, box, erase=None):
         """One small H2D copy: kernel gather indices, labels (int64 [B] each) and boxes (int32
-        [B, 5]) in one pinned buffer. Returns the three device views."""
+        [B, 5]) in one pinned buffer -- with ``erase``, its rectangles and keys behind them.
+        Returns the three device views and, with ``erase``, the pair ``(erect, ekey)``."""
         B = len(kidx)
-        host = torch.empty(9 * B, dtype=torch.int32, pin_memory=True)
+        host = torch.empty(9 * B + self._erase_words(erase, B), dtype=torch.int32, pin_memory=True)
         host[:2 * B].view(torch.int64).copy_(torch.from_numpy(np.ascontiguousarray(kidx, dtype=np.int64)))
         host[2 * B:4 * B].view(torch.int64).copy_(torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int64)))
-        host[4 * B:].view(B, 5).copy_(box)
+        host[4 * B:9 * B].view(B, 5).copy_(box)
+        if erase is not None:
+            self._put_erase(host, 9 * B, erase)
         dev = host.to(self.device, non_blocking=True)
-        return dev[:2 * B].view(torch.int64), dev[2 * B:4 * B].view(torch.int64), dev[4 * B:].view(B, 5)
+        views = dev[:2 * B].view(torch.int64), dev[2 * B:4 * B].view(torch.int64), dev[4 * B:9 * B].view(B, 5)
+        return views if erase is None else views + (self._erase_views(dev, 9 * B, erase),)
 
-    def _upload_mixed(self, kidx, labels, box, mix):
+    def _upload_mixed(self, kidx, labels, box, mix, erase=None):
         """:meth:`_upload_params` of a mixed batch, still one pinned buffer and one H2D copy: the
         gather indices, labels and boxes of the samples and of their partners (``kidx[partner]``:
         in staged mode the partner is read from the same staging slot), the rectangles, ``w_own``
-        and ``lam``. Returns ``(kidx, box, pidx, pbox, rect, w_own)`` and the MixedTarget."""
+        and ``lam`` -- with ``erase``, its rectangles and keys behind them. Returns ``(kidx, box,
+        pidx, pbox, rect, w_own)``, the MixedTarget and, with ``erase``, the pair ``(erect, ekey)``."""
         partner, w_own, rect, lam = mix
         B = len(kidx)
         kidx = torch.from_numpy(np.ascontiguousarray(kidx, dtype=np.int64))
         labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int64))
-        host = torch.empty(24 * B, dtype=torch.int32, pin_memory=True)
+        host = torch.empty(24 * B + self._erase_words(erase, B), dtype=torch.int32, pin_memory=True)
         i64 = host[:8 * B].view(torch.int64).view(4, B)  # the int64 vectors first: 8-byte aligned for any B
         i64[0], i64[1], i64[2], i64[3] = kidx, labels, kidx[partner], labels[partner]
         host[8 * B:13 * B].view(B, 5).copy_(box)
         host[13 * B:18 * B].view(B, 5).copy_(box[partner])
         host[18 * B:22 * B].view(B, 4).copy_(rect)
         host[22 * B:23 * B].view(torch.float32).copy_(w_own)
-        host[23 * B:].view(torch.float32).copy_(lam)
+        host[23 * B:24 * B].view(torch.float32).copy_(lam)
+        if erase is not None:
+            self._put_erase(host, 24 * B, erase)
         dev = host.to(self.device, non_blocking=True)
         d64 = dev[:8 * B].view(torch.int64).view(4, B)
         args = (d64[0], dev[8 * B:13 * B].view(B, 5), d64[2], dev[13 * B:18 * B].view(B, 5),
                 dev[18 * B:22 * B].view(B, 4), dev[22 * B:23 * B].view(torch.float32))
-        return args, MixedTarget(d64[1], d64[3], dev[23 * B:].view(torch.float32))
+        target = MixedTarget(d64[1], d64[3], dev[23 * B:24 * B].view(torch.float32))
+        return (args, target) if erase is None else (args, target, self._erase_views(dev, 24 * B, erase))
 
-    def _batch(self, src, kidx, labels, box, mix):
+    def _batch(self, src, kidx, labels, box, mix, erase=None):
         """Upload one batch's parameters and launch: ``(images, labels or MixedTarget)``."""
+        if erase is None:
+            if mix is None:
+                kidx_d, y, box_d = self._upload_params(kidx, labels, box)
+                return self._launch(src, kidx_d, box_d), y
+            (kidx_d, box_d, *mixed), target = self._upload_mixed(kidx, labels, box, mix)
+            return self._launch(src, kidx_d, box_d, mixed), target
         if mix is None:
-            kidx_d, y, box_d = self._upload_params(kidx, labels, box)
-            return self._launch(src, kidx_d, box_d), y
-        (kidx_d, box_d, *mixed), target = self._upload_mixed(kidx, labels, box, mix)
-        return self._launch(src, kidx_d, box_d, mixed), target
+            kidx_d, y, box_d, erased = self._upload_params(kidx, labels, box, erase)
+            return self._launch(src, kidx_d, box_d, None, erased), y
+        (kidx_d, box_d, *mixed), target, erased = self._upload_mixed(kidx, labels, box, mix, erase)
+        return self._launch(src, kidx_d, box_d, mixed, erased), target
 
-    def _launch(self, src, kidx, box, mixed=None):
+    def _launch(self, src, kidx, box, mixed=None, erased=None):
         from ..ops import native_ops
         B, S = box.shape[0], self.image_size
         buf = torch.empty((B, S, S, 4), dtype=torch.bfloat16, device=self.device)
-        if mixed is None:
+        if erased is not None:
+            native_ops.crop_resize_normalize_erase(src, kidx, box, mixed, *erased, self.re_mode, buf, self.mean,
+                                                   self.std)
+        elif mixed is None:
             native_ops.crop_resize_normalize(src, kidx, box, buf, self.mean, self.std)
         else:
             native_ops.crop_resize_normalize_mix(src, kidx, box, *mixed, buf, self.mean, self.std)
@@ -556,7 +758,8 @@ class PackedImageLoader:
         epoch = self.epoch
         for indices in self._index_batches():
             idx = validate_indices(indices, len(ds))
-            yield self._batch(src, idx, ds.labels[idx], self.boxes(indices, epoch), self.mix(indices, epoch))
+            yield self._batch(src, idx, ds.labels[idx], self.boxes(indices, epoch), self.mix(indices, epoch),
+                              self.erase(indices, epoch))
 
     def _staging_ring(self):
         if self._ring is None:
@@ -617,6 +820,7 @@ class PackedImageLoader:
                     idx = validate_indices(indices, len(ds))
                     box = self.boxes(indices, epoch)
                     mix = self.mix(indices, epoch)
+                    erase = self.erase(indices, epoch)
                     order = np.argsort(idx, kind="stable")
                     B = len(idx)
                     np.take(ds.images, idx[order], axis=0, out=pinned[:B].numpy())
@@ -627,7 +831,7 @@ class PackedImageLoader:
                         ev = torch.cuda.Event()
                         ev.record(side)
                     copied[slot] = ev
-                    if not put(("batch", slot, B, kidx, ds.labels[idx], box, mix, ev)):
+                    if not put(("batch", slot, B, kidx, ds.labels[idx], box, mix, erase, ev)):
                         return
                 put(("end",))
             except BaseException as e:  # re-raised in the consumer
@@ -643,10 +847,10 @@ class PackedImageLoader:
                     break
                 if item[0] == "error":
                     raise item[1]
-                _, slot, B, kidx, labels, box, mix, ev = item
+                _, slot, B, kidx, labels, box, mix, erase, ev = item
                 cur = torch.cuda.current_stream(self.device)
                 cur.wait_event(ev)
-                x, y = self._batch(ring[slot][1], kidx, labels, box, mix)
+                x, y = self._batch(ring[slot][1], kidx, labels, box, mix, erase)
                 rel = torch.cuda.Event()
                 rel.record(cur)
                 release_ev[slot] = rel

@@ -90,6 +90,58 @@ def crop_resize_normalize_mix(src, idx, box, pidx, pbox, rect, w_own, out, mean,
                                                   ctypes.addressof(inv), _s()), "crop_resize_norm_mix")
 
 
+_ERASE_MODES = {"const": 0, "pixel": 1}
+
+
+def crop_resize_normalize_erase(src, idx, box, mixed, erect, ekey, mode, out, mean, std):
+    """:func:`crop_resize_normalize` (``mixed`` None) or :func:`crop_resize_normalize_mix`
+    (``mixed = (pidx, pbox, rect, w_own)``) with Random Erasing in the same launch: a pixel of output
+    ``b`` inside any of its rectangles ``erect[b, r] = (y0, x0, y1, x1)`` (half-open, output
+    coordinates; empty when ``y0 == y1`` or ``x0 == x1``) loads nothing and is +0 (``mode``
+    ``"const"``) or an N(0, 1) draw per channel (``"pixel"``: a counter-based hash of ``ekey[b]``,
+    the pixel and the channel, Box-Muller, rounded once to bf16 -- the formula in
+    ``csrc/image_aug.hip``). Every other pixel, and the pad channel, are the bits the call without
+    erasing writes.
+
+    ``erect`` int32 [B, R, 4] inside ``[0, S]^2``, R in 1..8; ``ekey`` int32 [B] holding the uint32
+    keys' bits; the rest as in the two functions above. The kernel trusts them all: validate on the
+    host (``data/packed.py``: ``validate_erase``)."""
+    assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and src.is_contiguous()
+    assert out.dtype == torch.bfloat16 and out.dim() == 4 and out.is_contiguous() and out.device == src.device
+    B, S, S2, Cp = out.shape
+    assert S == S2 and Cp % 4 == 0 and B > 0
+    assert box.dtype == torch.int32 and tuple(box.shape) == (B, 5) and box.is_contiguous() and box.device == src.device
+    if idx is not None:
+        assert idx.dtype == torch.int64 and tuple(idx.shape) == (B,) and idx.is_contiguous() \
+            and idx.device == src.device
+    else:
+        assert src.shape[0] >= B
+    pidx = pbox = rect = w_own = None
+    if mixed is not None:
+        pidx, pbox, rect, w_own = mixed
+        assert pidx.dtype == torch.int64 and tuple(pidx.shape) == (B,) and pidx.is_contiguous() \
+            and pidx.device == src.device
+        assert pbox.dtype == torch.int32 and tuple(pbox.shape) == (B, 5) and pbox.is_contiguous() \
+            and pbox.device == src.device
+        assert rect.dtype == torch.int32 and tuple(rect.shape) == (B, 4) and rect.is_contiguous() \
+            and rect.device == src.device
+        assert w_own.dtype == torch.float32 and tuple(w_own.shape) == (B,) and w_own.is_contiguous() \
+            and w_own.device == src.device
+    assert erect.dtype == torch.int32 and erect.dim() == 3 and erect.shape[0] == B and 1 <= erect.shape[1] <= 8 \
+        and erect.shape[2] == 4 and erect.is_contiguous() and erect.device == src.device
+    assert ekey.dtype == torch.int32 and tuple(ekey.shape) == (B,) and ekey.is_contiguous() \
+        and ekey.device == src.device
+    assert mode in _ERASE_MODES, mode
+    assert len(mean) == 3 and len(std) == 3 and all(float(s) > 0 for s in std)
+    m = (c_float * 3)(*[float(v) for v in mean])
+    inv = (c_float * 3)(*[1.0 / float(v) for v in std])
+    n, Hs, Ws, _ = src.shape
+    _chk(_load().pdt_crop_resize_norm_erase_u8_bf16(_p(src), Hs, Ws, _p(idx), _p(box), _p(pidx), _p(pbox), _p(rect),
+                                                    _p(w_own), _p(erect), int(erect.shape[1]), _p(ekey),
+                                                    _ERASE_MODES[mode], _p(out), B, S, Cp, ctypes.addressof(m),
+                                                    ctypes.addressof(inv), _s()), "crop_resize_norm_erase")
+
+
 def synthetic_images(shape, dtype, device, seed=0, channels_last=True):
     n, c, h, w = shape
     if channels_last:

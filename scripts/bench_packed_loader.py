@@ -17,6 +17,10 @@ profiles/packed_loader.txt).
    all-CutMix, all-Mixup -- against the plain entry point, three rounds of each for the run-to-run
    spread; and with training, ResNet-50 steps/s with a mixing loader against the same loader
    without mixing.
+5. ``--erase``: the launch with Random Erasing (pdt_crop_resize_norm_erase_u8_bf16) beside the plain
+   and the mixing entry points of the same build, three alternating rounds each: nothing to erase,
+   re_prob 0.25 with drawn rectangles in both modes, every sample erased, and erasing on top of
+   all-Mixup.
 
 A run without a GPU fails: nothing here falls back to the CPU.
 """
@@ -136,6 +140,52 @@ def bench_mix_kernel(B, dev):
     base = min(times["plain entry point"])
     for name, t in times.items():
         print(f"{name:28s}: " + ", ".join(f"{x:.3f}" for x in t) + f" ms   (best / plain best = {min(t) / base:.2f}x)")
+
+
+def bench_erase_kernel(B, dev):
+    print(f"== erasing launch: B={B}, 256x256x3 uint8 store -> 224x224x4 bf16, RandomResizedCrop boxes, "
+          "pdt_crop_resize_norm_erase_u8_bf16 beside the plain and the mixing entry points")
+    from pytorch_distributed_template_amd.data import erase_keys, mix_params, random_erasing_rects
+    from pytorch_distributed_template_amd.data.packed import u32_bits
+    Hs = Ws = 256
+    S = 224
+    n_src = min(B, 4096)
+    src = torch.randint(0, 256, (n_src, Hs, Ws, 3), dtype=torch.uint8, device=dev)
+    idx = (torch.randperm(B, device=dev) % n_src).to(torch.int64)
+    box = random_resized_crop_boxes(torch.arange(B), 0, 0, Hs, Ws).to(dev)
+    pidx, pbox = idx.flip(0).contiguous(), box.flip(0).contiguous()
+    out = torch.empty((B, S, S, 4), dtype=torch.bfloat16, device=dev)
+    _, w_own, rect, _ = mix_params(list(range(B)), 0, 0, S, mix_mode="elem", mixup_alpha=0.8)
+    mixed = (pidx, pbox, rect.to(dev), w_own.to(dev))
+    ekey = u32_bits(erase_keys(torch.arange(B), 0, 0)).to(dev)
+    rects = {p: random_erasing_rects(torch.arange(B), 0, 0, S, re_prob=p) for p in (0.0, 0.25, 1.0)}
+    for p, r in rects.items():
+        area = ((r[..., 2] - r[..., 0]).long() * (r[..., 3] - r[..., 1]).long()).sum().item() / (B * S * S)
+        print(f"re_prob {p}: {int((r[:, 0, 2] > r[:, 0, 0]).sum())} of {B} samples erased, {100 * area:.1f} % of the pixels")
+    rects = {p: r.to(dev) for p, r in rects.items()}
+
+    def erase(p, mode, mix=None):
+        return lambda: native_ops.crop_resize_normalize_erase(src, idx, box, mix, rects[p], ekey, mode, out, MEAN, STD)
+    variants = {
+        "plain entry point": lambda: native_ops.crop_resize_normalize(src, idx, box, out, MEAN, STD),
+        "erase entry point, nothing to erase": erase(0.0, "pixel"),
+        "re_prob 0.25, pixel": erase(0.25, "pixel"),
+        "re_prob 0.25, const": erase(0.25, "const"),
+        "every sample erased, pixel": erase(1.0, "pixel"),
+        "every sample erased, const": erase(1.0, "const"),
+        "mix entry point, all Mixup (alpha 0.8)": lambda: native_ops.crop_resize_normalize_mix(src, idx, box, *mixed, out,
+                                                                                              MEAN, STD),
+        "all Mixup, nothing to erase": erase(0.0, "pixel", mixed),
+        "all Mixup, re_prob 0.25, pixel": erase(0.25, "pixel", mixed),
+        "all Mixup, every sample erased, pixel": erase(1.0, "pixel", mixed),
+    }
+    times = {k: [] for k in variants}
+    for _ in range(3):
+        for name, fn in variants.items():
+            times[name].append(event_ms(fn))
+    base = min(times["plain entry point"])
+    for name, t in times.items():
+        print(f"{name:40s}: " + ", ".join(f"{x:.3f}" for x in t) + f" ms   (best / plain best = {min(t) / base:.2f}x)")
 
 
 def bench_train_mix(data_dir, batch, dev):
@@ -263,6 +313,7 @@ def main():
     ap.add_argument("--skip-train", action="store_true")
     ap.add_argument("--skip-feed", action="store_true")
     ap.add_argument("--mix", action="store_true", help="measure the Mixup / CutMix launch and training with it instead")
+    ap.add_argument("--erase", action="store_true", help="measure the Random Erasing launch instead")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_packed_loader.py needs a GPU")
@@ -270,6 +321,9 @@ def main():
     dev = torch.device("cuda", torch.cuda.current_device())
     print(f"device: {torch.cuda.get_device_name(dev)}; torch {torch.__version__}; host CPUs used: "
           f"{os.environ.get('OMP_NUM_THREADS', 'all')}")
+    if a.erase:
+        bench_erase_kernel(a.batch, dev)
+        return
     if a.mix:
         bench_mix_kernel(a.batch, dev)
         if not a.skip_train:
