@@ -7,16 +7,38 @@
 // fp32 master params / grads / states; optionally a bf16 shadow copy of each
 // param is written in the same pass (the copy the bf16 conv/GEMM kernels read),
 // so no separate cast kernel runs per step.
+#include <cfloat>
+
 #include "optim_common.h"
 
 namespace {
 
+// The GUARD instantiations (the ..._step3 entry points) take two more kernel arguments, the
+// pack G = (const float* glob, int skip_nonfinite): glob[2] is the global gradient norm before
+// clipping and glob[3] the clip coefficient (csrc/optim_layerwise.hip: norm_finalize_kernel),
+// both read once per workgroup into scalar registers. Each gradient is multiplied by
+// clip * grad_scale, and with skip_nonfinite a norm that is inf or NaN ends the workgroup
+// before its first load of a tensor, so that launch stores nothing. Without GUARD the pack is
+// empty and the kernels are what they were before the flag existed, instruction for
+// instruction (profiles/optim_clip.txt).
+//
+// Folds the clip coefficient into grad_scale; false: decline the step.
+__device__ __forceinline__ bool guard_scale(float& grad_scale, const float* __restrict__ glob, int skip_nonfinite) {
+  if (skip_nonfinite && !(glob[2] <= FLT_MAX)) return false;
+  grad_scale *= glob[3];
+  return true;
+}
+
 // SGD (torch semantics): g += wd*p; buf = mom*buf + (1-damp)*g (buf = g on
 // first step); g = nesterov ? g + mom*buf : buf; p -= lr*g
+template <bool GUARD, typename... G>
 __global__ void sgd_kernel(const Chunk* __restrict__ chunks, int nchunks, float* const* __restrict__ params,
                            const float* const* __restrict__ grads, float* const* __restrict__ bufs,
                            u16* const* __restrict__ shadows, float lr, float momentum, float dampening, float wd,
-                           int nesterov, int first, float grad_scale, const float* __restrict__ dev) {
+                           int nesterov, int first, float grad_scale, const float* __restrict__ dev, G... guard) {
+  if constexpr (GUARD) {
+    if (!guard_scale(grad_scale, guard...)) return;
+  }
   if (dev != nullptr) lr = dev[0];  // capturable: the lr a replayed graph must not freeze
   // one element: returns the new parameter, updates the momentum buffer value in place
   auto upd = [&](float gi, float pi, float& bi, bool has_b) {
@@ -65,11 +87,16 @@ __global__ void sgd_kernel(const Chunk* __restrict__ chunks, int nchunks, float*
 }
 
 // Adam / AdamW (decoupled=1), optional AMSGrad. bc1 = 1-b1^t, bc2 = 1-b2^t.
+template <bool GUARD, typename... G>
 __global__ void adam_kernel(const Chunk* __restrict__ chunks, int nchunks, float* const* __restrict__ params,
                             const float* const* __restrict__ grads, float* const* __restrict__ exp_avg,
                             float* const* __restrict__ exp_avg_sq, float* const* __restrict__ max_sq,
                             u16* const* __restrict__ shadows, float lr, float b1, float b2, float eps, float wd,
-                            int decoupled, float bc1, float bc2, float grad_scale, const float* __restrict__ dev) {
+                            int decoupled, float bc1, float bc2, float grad_scale, const float* __restrict__ dev,
+                            G... guard) {
+  if constexpr (GUARD) {
+    if (!guard_scale(grad_scale, guard...)) return;
+  }
   if (dev != nullptr) {  // capturable: lr and the step count t live in device memory
     lr = dev[0];
     bc1 = 1.f - powf(b1, dev[1]);
@@ -114,6 +141,18 @@ __global__ void opt_tick_kernel(float* dev) {
   if (threadIdx.x == 0) dev[1] += 1.f;
 }
 
+// The tick under skip_nonfinite, making the step kernels' test: on a finite norm t += 1 (dev
+// may be null: nothing counts steps on the device), otherwise *skipped += 1 (skipped may be
+// null: another launch of this step counts it). One thread.
+__global__ void opt_tick_guard_kernel(float* dev, const float* __restrict__ glob, int* skipped) {
+  if (threadIdx.x != 0) return;
+  if (glob[2] <= FLT_MAX) {
+    if (dev != nullptr) dev[1] += 1.f;
+  } else if (skipped != nullptr) {
+    *skipped += 1;
+  }
+}
+
 }  // namespace
 
 PDT_API int pdt_chunk_struct_size() { return (int)sizeof(Chunk); }
@@ -125,9 +164,29 @@ PDT_API int pdt_chunk_struct_size() { return (int)sizeof(Chunk); }
 PDT_API int pdt_sgd_step2(const void* chunks, int nchunks, void* params, const void* grads, void* bufs, void* shadows,
                           float lr, float momentum, float dampening, float wd, int nesterov, int first,
                           float grad_scale, const float* dev, hipStream_t st) {
-  hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(nchunks)), dim3(NT), 0, st, (const Chunk*)chunks, nchunks,
+  hipLaunchKernelGGL((sgd_kernel<false>), dim3(grid_for(nchunks)), dim3(NT), 0, st, (const Chunk*)chunks, nchunks,
                      (float* const*)params, (const float* const*)grads, (float* const*)bufs,
                      (u16* const*)shadows, lr, momentum, dampening, wd, nesterov, first, grad_scale, dev);
+  PDT_RETURN_LAUNCH();
+}
+
+// pdt_sgd_step2 with the global gradient norm and clip coefficient read from glob (guard_scale).
+// skipped (optional, with skip_nonfinite): a one-thread launch adds 1 to it when the step is
+// declined; the caller passes it with one launch per optimizer step.
+PDT_API int pdt_sgd_step3(const void* chunks, int nchunks, void* params, const void* grads, void* bufs, void* shadows,
+                          float lr, float momentum, float dampening, float wd, int nesterov, int first,
+                          float grad_scale, const float* dev, const float* glob, int skip_nonfinite, int* skipped,
+                          hipStream_t st) {
+  if (glob == nullptr) return -1;
+  if (skip_nonfinite && skipped != nullptr) {
+    hipLaunchKernelGGL(opt_tick_guard_kernel, dim3(1), dim3(64), 0, st, (float*)nullptr, glob, skipped);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL((sgd_kernel<true, const float*, int>), dim3(grid_for(nchunks)), dim3(NT), 0, st,
+                     (const Chunk*)chunks, nchunks, (float* const*)params, (const float* const*)grads,
+                     (float* const*)bufs, (u16* const*)shadows, lr, momentum, dampening, wd, nesterov, first,
+                     grad_scale, dev, glob, skip_nonfinite);
   PDT_RETURN_LAUNCH();
 }
 
@@ -141,9 +200,32 @@ PDT_API int pdt_adam_step2(const void* chunks, int nchunks, void* params, const 
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
   }
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(nchunks)), dim3(NT), 0, st, (const Chunk*)chunks, nchunks,
+  hipLaunchKernelGGL((adam_kernel<false>), dim3(grid_for(nchunks)), dim3(NT), 0, st, (const Chunk*)chunks, nchunks,
                      (float* const*)params, (const float* const*)grads, (float* const*)exp_avg,
                      (float* const*)exp_avg_sq, (float* const*)max_sq, (u16* const*)shadows, lr, b1, b2, eps, wd,
                      decoupled, bc1, bc2, grad_scale, (const float*)dev);
+  PDT_RETURN_LAUNCH();
+}
+
+// pdt_adam_step2 with the global gradient norm and clip coefficient read from glob (see
+// guard_scale). With skip_nonfinite the tick is the guarded one: t does not advance on a declined
+// step, and skipped (optional, passed with one launch per optimizer step) counts it.
+PDT_API int pdt_adam_step3(const void* chunks, int nchunks, void* params, const void* grads, void* exp_avg,
+                           void* exp_avg_sq, void* max_sq, void* shadows, float lr, float b1, float b2, float eps,
+                           float wd, int decoupled, float bc1, float bc2, float grad_scale, float* dev, int tick,
+                           const float* glob, int skip_nonfinite, int* skipped, hipStream_t st) {
+  if (glob == nullptr || (tick && dev == nullptr)) return -1;
+  if (skip_nonfinite && (tick || skipped != nullptr)) {
+    hipLaunchKernelGGL(opt_tick_guard_kernel, dim3(1), dim3(64), 0, st, tick ? dev : (float*)nullptr, glob,
+                       skipped);
+  } else if (tick) {
+    hipLaunchKernelGGL(opt_tick_kernel, dim3(1), dim3(64), 0, st, dev);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL((adam_kernel<true, const float*, int>), dim3(grid_for(nchunks)), dim3(NT), 0, st,
+                     (const Chunk*)chunks, nchunks, (float* const*)params, (const float* const*)grads,
+                     (float* const*)exp_avg, (float* const*)exp_avg_sq, (float* const*)max_sq, (u16* const*)shadows, lr, b1, b2, eps, wd,
+                     decoupled, bc1, bc2, grad_scale, (const float*)dev, glob, skip_nonfinite);
   PDT_RETURN_LAUNCH();
 }

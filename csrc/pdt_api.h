@@ -275,6 +275,14 @@ PDT_API int pdt_adam_step2(const void* chunks, int nchunks, void* params, const 
                            void* exp_avg_sq, void* max_sq, void* shadows, float lr, float b1, float b2, float eps,
                            float wd, int decoupled, float bc1, float bc2, float grad_scale, float* dev, int tick,
                            hipStream_t st);
+PDT_API int pdt_sgd_step3(const void* chunks, int nchunks, void* params, const void* grads, void* bufs, void* shadows,
+                          float lr, float momentum, float dampening, float wd, int nesterov, int first,
+                          float grad_scale, const float* dev, const float* glob, int skip_nonfinite, int* skipped,
+                          hipStream_t st);
+PDT_API int pdt_adam_step3(const void* chunks, int nchunks, void* params, const void* grads, void* exp_avg,
+                           void* exp_avg_sq, void* max_sq, void* shadows, float lr, float b1, float b2, float eps,
+                           float wd, int decoupled, float bc1, float bc2, float grad_scale, float* dev, int tick,
+                           const float* glob, int skip_nonfinite, int* skipped, hipStream_t st);
 
 // optim_layerwise.hip
 PDT_API int pdt_sumsq_chunks(const void* chunks, int nchunks, const void* a, const void* b, float* partials,

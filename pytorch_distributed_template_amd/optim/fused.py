@@ -27,6 +27,12 @@ a group to receive a gradient on every step (a captured graph assumes that anywa
 torch's per-parameter counts would diverge from the group count there, and a checkpoint
 reloaded into torch.optim would apply different bias corrections.
 
+``max_grad_norm`` / ``skip_nonfinite`` (``_ClippedBase``): the three clip the global gradient
+norm on the device -- the norm launches of the layer-wise optimizers, then the guarded step
+kernels, which read the norm and the clip coefficient from device memory -- and decline a step
+whose norm is inf or NaN, with no host sync, eagerly and in a captured step alike. Both off,
+a step issues exactly the launches described above.
+
 ``FusedLARS`` / ``FusedLAMB`` (second half of this file, ``csrc/optim_layerwise.hip``) are the
 layer-wise optimizers of the large-batch recipes, with global gradient-norm clipping on the
 device; they are built on ``multi_tensor_l2norm``, a deterministic per-tensor L2 norm whose
@@ -121,6 +127,33 @@ class _Plan:
         return None if t is None else t.data_ptr()
 
 
+class _NormTables:
+    """What the norm kernels need next to a ``_Plan``: ``chunk_begin[n + 1]`` (a tensor's
+    chunks are consecutive in the chunk table), ``flags[n]`` (bit 0: layer-wise adaptation and
+    weight decay apply), the per-chunk partial sums and the per-tensor norms ``[2, n]``."""
+
+    def __init__(self, plan, params, adapt):
+        import numpy as np
+        n = len(params)
+        begin = np.zeros(n + 1, dtype=np.int32)
+        begin[1:] = np.cumsum([(p.numel() + CHUNK - 1) // CHUNK for p in params])
+        assert int(begin[-1]) == plan.nchunks, (int(begin[-1]), plan.nchunks)
+        dev = plan.device
+        self.key = tuple(adapt)
+        self.n = n
+        self.chunk_begin = _to_device_async(torch.from_numpy(begin), dev)
+        self.flags = _to_device_async(torch.tensor([int(a) for a in adapt], dtype=torch.int32), dev)
+        self.partials = torch.zeros(2 * max(plan.nchunks, 1), dtype=torch.float32, device=dev)
+        self.norms = torch.zeros((2, max(n, 1)), dtype=torch.float32, device=dev)
+
+
+def _norm_tables(plan, params, adapt):
+    nt = getattr(plan, "norm_tables", None)
+    if nt is None or nt.key != tuple(adapt):
+        nt = plan.norm_tables = _NormTables(plan, params, adapt)
+    return nt
+
+
 def _native_ok(params):
     return (len(params) > 0 and all(
         p.is_cuda and p.dtype == torch.float32 and (
@@ -145,19 +178,29 @@ class _FusedBase(Optimizer):
     ``(group index, group, its parameters with a gradient)``. Without ``whole_step_fallback``
     every group takes the native path if it passes ``_native_ok`` and the torch path if not
     (``work`` then holds one group per call); with it, one failing group sends the whole step
-    down the torch path."""
+    down the torch path.
+
+    ``max_grad_norm`` / ``skip_nonfinite`` are optimizer-wide: the global gradient norm spans
+    every param group (one device buffer, combined over the groups in group order), so with
+    either set ``whole_step_fallback`` holds."""
     whole_step_fallback = False
     dev_width = 2  # floats of a group's device scalars
 
-    def __init__(self, params, defaults, write_bf16_shadow=True, capturable=False):
+    def __init__(self, params, defaults, write_bf16_shadow=True, capturable=False, max_grad_norm=0.0,
+                 skip_nonfinite=False):
         super().__init__(params, defaults)
         self.write_bf16_shadow = write_bf16_shadow
         self.capturable = bool(capturable)
+        self.max_grad_norm = float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
         self._plans = {}
         self._shadows = {}
-        self._dev = {}      # capturable: group index -> device [lr, t]
+        self._dev = {}      # group index -> device [lr, t] (capturable; Adam with skip_nonfinite)
         self._dev_lr = {}   # the lr last written into it
-        self._grad_sets = {}  # capturable Adam: group index -> ids of the params stepped first
+        self._grad_sets = {}  # device-counted Adam: group index -> ids of the params stepped first
+        self._glob = None   # device [sum of squares (one double), gnorm, clip]
+        self._gnorm = None  # the last step's global gradient norm (0-d; into _glob on the native path)
+        self._skipped = None  # device int32 [1]: the steps skip_nonfinite declined
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -192,8 +235,9 @@ class _FusedBase(Optimizer):
 
     def _write_back_steps(self):
         """Capturable mode: set each parameter's ``step`` from its group's device step count
-        (replayed graphs advance only that), so that ``state_dict()`` stays torch's."""
-        if not self.capturable:
+        (replayed graphs advance only that, and a step ``skip_nonfinite`` declined does not
+        advance it), so that ``state_dict()`` stays torch's."""
+        if not self._dev:
             return
         for gi, group in enumerate(self.param_groups):
             d = self._dev.get(gi)
@@ -204,11 +248,13 @@ class _FusedBase(Optimizer):
                 if p in self.state and "step" in self.state[p]:
                     self.state[p]["step"] = torch.tensor(t)
 
-    def _adam_moments(self, name, work, dev_step):
+    def _adam_moments(self, name, work, dev_step, ok=None):
         """Adam's state for ``work``: created (``max_exp_avg_sq`` too in an ``amsgrad`` group) on a
         parameter's first step, and ``step`` advanced unless the device counts it (``dev_step``:
         the parameters with gradients must then be the same on every step). Returns this step's
-        ``{group index: (bc1, bc2)}``."""
+        ``{group index: (bc1, bc2)}``. With ``ok`` (the torch path under ``skip_nonfinite``: a
+        0-d bool tensor) ``step`` advances by it, next to the parameter, and the bias corrections
+        are 0-d tensors: nothing here reads the predicate on the host."""
         bcs = {}
         for gi, group, params in work:
             if dev_step:
@@ -227,10 +273,13 @@ class _FusedBase(Optimizer):
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     if group.get("amsgrad"):
                         st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                if not dev_step:  # (capturable: the device count is the step, see _write_back_steps)
+                if ok is not None:
+                    st["step"] = st["step"].to(ok.device) + ok.to(torch.float32)
+                elif not dev_step:  # (capturable: the device count is the step, see _write_back_steps)
                     st["step"] += 1
             b1, b2 = group["betas"]
-            step = float(self.state[params[0]]["step"]) if not dev_step else 1.0
+            step = self.state[params[0]]["step"]
+            step = step if ok is not None else float(step) if not dev_step else 1.0
             bcs[gi] = (1 - b1 ** step, 1 - b2 ** step)
         return bcs
 
@@ -280,8 +329,8 @@ class _FusedBase(Optimizer):
     def refresh_scalars(self):
         """Write each group's current lr into its device scalars (capturable mode): call it
         before replaying a graph that captured ``step()`` -- an LR scheduler changes only the
-        host value. A no-op for groups whose lr did not change (and outside capturable mode)."""
-        if not self.capturable:
+        host value. A no-op for groups whose lr did not change (and without device scalars)."""
+        if not self._dev:
             return
         for gi, group in enumerate(self.param_groups):
             d = self._dev.get(gi)
@@ -308,7 +357,7 @@ class _FusedBase(Optimizer):
             torch._foreach_zero_(grads)
 
     def _step_prologue(self):
-        if self.capturable and not torch.cuda.is_current_stream_capturing():
+        if self._dev and not torch.cuda.is_current_stream_capturing():
             self.refresh_scalars()
 
     def load_state_dict(self, state_dict):
@@ -340,105 +389,282 @@ class _FusedBase(Optimizer):
     def _stream():
         return torch.cuda.current_stream().cuda_stream
 
+    # ---- the global gradient norm: clipping (max_grad_norm) and skip_nonfinite
+    @staticmethod
+    def _adapt(group, p):
+        return False
 
-class FusedSGD(_FusedBase):
-    """torch.optim.SGD semantics (momentum, dampening, nesterov, weight_decay)."""
+    def _global(self, device):
+        if self._glob is None or self._glob.device != device:
+            self._glob = torch.zeros(4, dtype=torch.float32, device=device)
+            self._glob[3] = 1.0
+        self._gnorm = self._glob[2]
+        return self._glob
+
+    def _tables(self, gi, group, params, roles):
+        plan = self._plan(gi, params, roles, params[0].device)
+        return plan, _norm_tables(plan, params, [self._adapt(group, p) for p in params])
+
+    def _sumsq(self, plan, nt, a, b):
+        _call("sumsq_chunks", plan.chunks.data_ptr(), plan.nchunks, plan.ptr(a), plan.ptr(b) if b else None,
+              nt.partials.data_ptr(), self._stream())
+
+    def _finalize(self, nt, nroles, grole, glob, start_zero):
+        _call("norm_finalize", nt.partials.data_ptr(), nt.chunk_begin.data_ptr(), nt.n, nroles, grole,
+              nt.norms.data_ptr(), glob.data_ptr() if glob is not None else None, int(start_zero),
+              self.max_grad_norm, self._stream())
+
+    def _torch_norm(self, work):
+        """The global gradient norm from an fp64 sum, 0-d fp64 (no host sync); kept, in fp32,
+        for ``grad_norm()``."""
+        sq = [p.grad.double().pow(2).sum() for _, _, params in work for p in params]
+        gnorm = torch.stack([s.to(sq[0].device) for s in sq]).sum().sqrt()
+        self._gnorm = gnorm.float()
+        return gnorm
+
+    def _torch_clip(self, work):
+        """The clip coefficient as a 0-d fp32 tensor (no host sync), or None without clipping."""
+        if self.max_grad_norm <= 0:
+            return None
+        return torch.clamp(self.max_grad_norm / (self._torch_norm(work) + 1e-6), max=1.0).float()
+
+    def _torch_guard(self, work):
+        """The torch path's ``(clip, ok)``: the clip coefficient as ``_torch_clip`` gives it and,
+        under ``skip_nonfinite``, the 0-d bool tensor the kernels' ``gnorm <= FLT_MAX`` is (None
+        without); a declined step is counted here."""
+        clip = self._torch_clip(work)
+        if not self.skip_nonfinite:
+            return clip, None
+        if clip is None:
+            self._torch_norm(work)
+        ok = torch.isfinite(self._gnorm)
+        self._skip_counter(ok.device).add_((~ok).to(torch.int32))
+        return clip, ok
+
+    def _skip_counter(self, device):
+        if self._skipped is None or self._skipped.device != device:
+            self._skipped = torch.zeros(1, dtype=torch.int32, device=device)
+        return self._skipped
+
+    def _guard_args(self, glob, first_launch):
+        """What a ``..._step3`` entry point takes after ``..._step2``'s arguments; the step's
+        first launch alone counts a declined step."""
+        count = self.skip_nonfinite and first_launch
+        return (glob.data_ptr(), int(self.skip_nonfinite),
+                self._skip_counter(glob.device).data_ptr() if count else None)
+
+    def grad_norm(self):
+        """The global gradient norm of the last step that took one, as a 0-d device tensor (before
+        clipping; no host sync), or None if no step has."""
+        return self._gnorm
+
+    def skipped_steps(self):
+        """How many steps ``skip_nonfinite`` declined, as a 0-d device int tensor (no host sync).
+        Not part of ``state_dict()``."""
+        if self._skipped is None:
+            params = [p for group in self.param_groups for p in group["params"]]
+            self._skip_counter(params[0].device)
+        return self._skipped[0]
+
+
+class _ClippedBase(_FusedBase):
+    """Shared by FusedSGD / FusedAdam / FusedAdamW: ``max_grad_norm`` and ``skip_nonfinite``.
+
+    With both at their defaults a step is what it is without them: one launch per param group
+    (``pdt_..._step2``). With either set the step is, for every group, a sum-of-squares pass
+    over its gradients and a finalize, which chain through one device buffer into the norm over
+    ALL groups and ``clip = min(1, max_grad_norm / (gnorm + 1e-6))``; then, for every group, the
+    step kernel's guarded instantiation (``pdt_..._step3``), which reads the two values from
+    device memory, scales each gradient by ``clip`` and, under ``skip_nonfinite``, stores nothing
+    when the norm is inf or NaN. No launch waits for the host and all of them are captured with
+    the step; the buffers a captured step uses are created by the eager warm-up step, as the
+    plans are. Under DDP the norm is computed from the averaged gradients, identical on every
+    rank, with no collective.
+
+    A non-finite norm clips to nothing useful (``inf * 0`` and ``NaN * 1`` are NaN), so only
+    ``skip_nonfinite`` protects the weights: the declined step leaves parameters, state, bf16
+    shadows and Adam's step count as they were and adds one to ``skipped_steps()``."""
+
+    def __init__(self, params, defaults, write_bf16_shadow, capturable, max_grad_norm, skip_nonfinite):
+        super().__init__(params, defaults, write_bf16_shadow, capturable, max_grad_norm, skip_nonfinite)
+        if self.max_grad_norm < 0:
+            raise ValueError(f"max_grad_norm must be >= 0 (0 disables clipping), got {max_grad_norm}")
+        self._guard = self.max_grad_norm > 0 or self.skip_nonfinite
+        if self._guard:  # the norm spans the groups: one that cannot run natively takes all along
+            self.whole_step_fallback = True
+
+    def _norm_launches(self, work, roles_of):
+        """Per group of ``work``: its shadows, pointer roles (``roles_of(group, params, shadows)``)
+        and plan; with the guard on, also its sum-of-squares and finalize launches. Returns the
+        device buffer of the norm (None with the guard off) and ``(gi, group, params, shadows,
+        plan, roles)`` per group -- the roles because a densified gradient is a temporary that
+        must live until its step is enqueued. Every finalize has run before the first step
+        launch, so that one reads the norm over all groups."""
+        glob = self._global(work[0][2][0].device) if self._guard else None
+        launches = []
+        for k, (gi, group, params) in enumerate(work):
+            shadows = [self._shadow(p) for p in params]
+            roles = roles_of(group, params, shadows)
+            if self._guard:
+                plan, nt = self._tables(gi, group, params, roles)
+                self._sumsq(plan, nt, "g", None)
+                self._finalize(nt, 1, 0, glob, k == 0)
+            else:
+                plan = self._plan(gi, params, roles, params[0].device)
+            launches.append((gi, group, params, shadows, plan, roles))
+        return glob, launches
+
+    @staticmethod
+    def _keep_unless(ok, tensors, olds):
+        """The torch path of a declined step: every tensor takes its old value back."""
+        for t, old in zip(tensors, olds):
+            t.copy_(torch.where(ok.to(t.device), t, old))
+
+
+class FusedSGD(_ClippedBase):
+    """torch.optim.SGD semantics (momentum, dampening, nesterov, weight_decay), and
+    ``max_grad_norm`` / ``skip_nonfinite`` (``_ClippedBase``: the global gradient norm is clipped
+    on the device; under DDP it is computed from the averaged gradients, identical on every rank,
+    with no collective).
+
+    The first-step flag (``buf = g``) is set on the host, which cannot know that the device
+    declined a step: after a declined first step the buffer is still zero and the next step
+    takes ``momentum * 0 + (1 - dampening) g``, which is ``g`` only without dampening. So
+    ``skip_nonfinite`` with ``dampening != 0`` raises."""
 
     def __init__(self, params, lr=0.1, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
-                 write_bf16_shadow=True, capturable=False):
+                 write_bf16_shadow=True, capturable=False, max_grad_norm=0.0, skip_nonfinite=False):
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                         nesterov=nesterov)
-        super().__init__(params, defaults, write_bf16_shadow, capturable)
+        super().__init__(params, defaults, write_bf16_shadow, capturable, max_grad_norm, skip_nonfinite)
+        if self.skip_nonfinite and any(group["dampening"] != 0 for group in self.param_groups):
+            raise ValueError("FusedSGD: skip_nonfinite needs dampening == 0 (after a declined first step the "
+                             "zeroed momentum buffer gives (1 - dampening) g where torch takes g)")
 
     def _native_step(self, work):
-        for gi, group, params in work:
-            mom = group["momentum"] != 0
+        firsts = {}
+
+        def roles_of(group, params, shadows):
             # ONE first-step flag for the group: a buffer created on a later step makes the
             # kernel take buf = g for every tensor of the group on that step
             first = False
             bufs = []
             for p in params:
                 st = self.state[p]
-                if mom:
+                if group["momentum"] != 0:
                     if "momentum_buffer" not in st or st["momentum_buffer"] is None:
                         st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                         first = True
                     bufs.append(st["momentum_buffer"])
                 else:
                     bufs.append(None)
-            shadows = [self._shadow(p) for p in params]
-            roles = {"p": params, "g": _dense_grads(params), "b": bufs, "s": shadows}
-            plan = self._plan(gi, params, roles, params[0].device)
+            firsts[id(group)] = first
+            return {"p": params, "g": _dense_grads(params), "b": bufs, "s": shadows}
+
+        glob, launches = self._norm_launches(work, roles_of)
+        for k, (gi, group, params, shadows, plan, _) in enumerate(launches):
+            mom = group["momentum"] != 0
             dev = self._dev_scalars(gi, group, params[0].device) if self.capturable else None
-            _call("sgd_step2", plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("g"),
-                  plan.ptr("b") if mom else None, plan.ptr("s") if self.write_bf16_shadow else None,
-                  float(group["lr"]), float(group["momentum"]), float(group["dampening"]),
-                  float(group["weight_decay"]), int(group["nesterov"]), int(first), 1.0,
-                  dev.data_ptr() if dev is not None else None, self._stream(), what="sgd_step")
+            args = (plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("g"),
+                    plan.ptr("b") if mom else None, plan.ptr("s") if self.write_bf16_shadow else None,
+                    float(group["lr"]), float(group["momentum"]), float(group["dampening"]),
+                    float(group["weight_decay"]), int(group["nesterov"]), int(firsts[id(group)]), 1.0,
+                    dev.data_ptr() if dev is not None else None)
+            if glob is None:
+                _call("sgd_step2", *args, self._stream(), what="sgd_step")
+            else:
+                _call("sgd_step3", *args, *self._guard_args(glob, k == 0), self._stream(), what="sgd_step")
             self._finish(params, shadows)
 
     def _torch_step(self, work):
+        clip, ok = self._torch_guard(work)
         for _, group, params in work:
             for p in params:
-                g = p.grad
+                g = p.grad if clip is None else p.grad * clip.to(p.device)
+                mom = group["momentum"] != 0
+                st = self.state[p] if mom else {}
+                if ok is not None:  # (a buffer this step creates goes back to zero, as the kernel leaves it)
+                    keep = [p, st["momentum_buffer"]] if mom and st.get("momentum_buffer") is not None else [p]
+                    olds = [t.clone() for t in keep]
                 if group["weight_decay"] != 0:
                     g = g.add(p, alpha=group["weight_decay"])
-                if group["momentum"] != 0:
-                    st = self.state[p]
+                if mom:
                     buf = st.get("momentum_buffer")
                     if buf is None:
                         buf = torch.clone(g).detach()
                         st["momentum_buffer"] = buf
+                        if ok is not None:
+                            keep, olds = keep + [buf], olds + [torch.zeros_like(buf)]
                     else:
                         buf.mul_(group["momentum"]).add_(g, alpha=1 - group["dampening"])
                     g = g.add(buf, alpha=group["momentum"]) if group["nesterov"] else buf
                 p.add_(g, alpha=-group["lr"])
+                if ok is not None:
+                    self._keep_unless(ok, keep, olds)
 
 
-class FusedAdam(_FusedBase):
-    """torch.optim.Adam semantics (L2 weight decay; ``amsgrad``)."""
+class FusedAdam(_ClippedBase):
+    """torch.optim.Adam semantics (L2 weight decay; ``amsgrad``), and ``max_grad_norm`` /
+    ``skip_nonfinite`` (``_ClippedBase``: the global gradient norm is clipped on the device; under
+    DDP it is computed from the averaged gradients, identical on every rank, with no collective).
+
+    A declined step must not advance the step count, and the host cannot know of one without a
+    sync: under ``skip_nonfinite`` the count lives in device memory as it does in capturable mode
+    (one per param group, advanced by the guarded tick kernel; the set of parameters with
+    gradients must not change between steps), and ``state_dict()`` writes it back, so a checkpoint
+    holds the number of steps actually taken."""
     decoupled = False
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False,
-                 write_bf16_shadow=True, capturable=False):
+                 write_bf16_shadow=True, capturable=False, max_grad_norm=0.0, skip_nonfinite=False):
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad)
-        super().__init__(params, defaults, write_bf16_shadow, capturable)
+        super().__init__(params, defaults, write_bf16_shadow, capturable, max_grad_norm, skip_nonfinite)
 
     def state_dict(self):
-        """torch's format (in capturable mode after ``_write_back_steps()``)."""
+        """torch's format (with a device step count after ``_write_back_steps()``)."""
         self._write_back_steps()
         return super().state_dict()
 
     def _native_step(self, work):
-        dev_step = self.capturable
+        dev_step = self.capturable or self.skip_nonfinite
         bcs = self._adam_moments("FusedAdam", work, dev_step)
-        for gi, group, params in work:
+
+        def roles_of(group, params, shadows):
+            return {"p": params, "g": _dense_grads(params), "m": [self.state[p]["exp_avg"] for p in params],
+                    "v": [self.state[p]["exp_avg_sq"] for p in params],
+                    "vm": [self.state[p].get("max_exp_avg_sq") if group["amsgrad"] else None for p in params],
+                    "s": shadows}
+
+        glob, launches = self._norm_launches(work, roles_of)
+        for k, (gi, group, params, shadows, plan, _) in enumerate(launches):
             b1, b2 = group["betas"]
             bc1, bc2 = bcs[gi]
-            shadows = [self._shadow(p) for p in params]
-            roles = {"p": params, "g": _dense_grads(params), "m": [self.state[p]["exp_avg"] for p in params],
-                     "v": [self.state[p]["exp_avg_sq"] for p in params],
-                     "vm": [self.state[p].get("max_exp_avg_sq") if group["amsgrad"] else None for p in params],
-                     "s": shadows}
-            plan = self._plan(gi, params, roles, params[0].device)
             dev = self._dev_scalars(gi, group, params[0].device, t0=float(self.state[params[0]]["step"])) \
                 if dev_step else None
-            _call("adam_step2", plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("g"), plan.ptr("m"),
-                  plan.ptr("v"), plan.ptr("vm") if group["amsgrad"] else None,
-                  plan.ptr("s") if self.write_bf16_shadow else None, float(group["lr"]), float(b1), float(b2),
-                  float(group["eps"]), float(group["weight_decay"]), int(self.decoupled), float(bc1), float(bc2), 1.0,
-                  dev.data_ptr() if dev is not None else None, int(dev is not None), self._stream(),
-                  what="adam_step")
+            args = (plan.chunks.data_ptr(), plan.nchunks, plan.ptr("p"), plan.ptr("g"), plan.ptr("m"),
+                    plan.ptr("v"), plan.ptr("vm") if group["amsgrad"] else None,
+                    plan.ptr("s") if self.write_bf16_shadow else None, float(group["lr"]), float(b1), float(b2),
+                    float(group["eps"]), float(group["weight_decay"]), int(self.decoupled), float(bc1), float(bc2),
+                    1.0, dev.data_ptr() if dev is not None else None, int(dev is not None))
+            if glob is None:
+                _call("adam_step2", *args, self._stream(), what="adam_step")
+            else:
+                _call("adam_step3", *args, *self._guard_args(glob, k == 0), self._stream(), what="adam_step")
             self._finish(params, shadows)
 
     def _torch_step(self, work):
-        bcs = self._adam_moments("FusedAdam", work, False)
+        clip, ok = self._torch_guard(work)
+        bcs = self._adam_moments("FusedAdam", work, False, ok)
         for gi, group, params in work:
             b1, b2 = group["betas"]
             bc1, bc2 = bcs[gi]
             for p in params:
                 st = self.state[p]
-                g = p.grad
+                g = p.grad if clip is None else p.grad * clip.to(p.device)
+                if ok is not None:
+                    keep = [p, st["exp_avg"], st["exp_avg_sq"]] + ([st["max_exp_avg_sq"]] if group["amsgrad"] else [])
+                    olds = [t.clone() for t in keep]
+                    bc1, bc2 = bc1.to(p.device), bc2.to(p.device)
                 if group["weight_decay"] != 0:
                     if self.decoupled:
                         p.mul_(1 - group["lr"] * group["weight_decay"])
@@ -451,49 +677,29 @@ class FusedAdam(_FusedBase):
                     torch.maximum(st["max_exp_avg_sq"], v, out=st["max_exp_avg_sq"])
                     v = st["max_exp_avg_sq"]
                 denom = (v.sqrt() / (bc2 ** 0.5)).add_(group["eps"])
-                p.addcdiv_(st["exp_avg"], denom, value=-group["lr"] / bc1)
+                if ok is None:
+                    p.addcdiv_(st["exp_avg"], denom, value=-group["lr"] / bc1)
+                else:  # (bc1 is a tensor, 0 on a declined first step: what that gives is discarded)
+                    p.sub_(st["exp_avg"] / denom * (group["lr"] / bc1).to(p.dtype))
+                    self._keep_unless(ok, keep, olds)
 
 
 class FusedAdamW(FusedAdam):
-    """torch.optim.AdamW semantics (decoupled weight decay)."""
+    """torch.optim.AdamW semantics (decoupled weight decay); ``max_grad_norm`` and
+    ``skip_nonfinite`` as in ``FusedAdam`` (under DDP the norm is computed from the averaged
+    gradients, identical on every rank, with no collective)."""
     decoupled = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False,
-                 write_bf16_shadow=True, capturable=False):
-        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, write_bf16_shadow, capturable)
+                 write_bf16_shadow=True, capturable=False, max_grad_norm=0.0, skip_nonfinite=False):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, write_bf16_shadow, capturable,
+                         max_grad_norm, skip_nonfinite)
 
 
 # =============================================================================
 # Layer-wise adaptive optimizers (LARS, LAMB) with on-device gradient-norm clipping
 # (csrc/optim_layerwise.hip)
 # =============================================================================
-class _NormTables:
-    """What the norm kernels need next to a ``_Plan``: ``chunk_begin[n + 1]`` (a tensor's
-    chunks are consecutive in the chunk table), ``flags[n]`` (bit 0: layer-wise adaptation and
-    weight decay apply), the per-chunk partial sums and the per-tensor norms ``[2, n]``."""
-
-    def __init__(self, plan, params, adapt):
-        import numpy as np
-        n = len(params)
-        begin = np.zeros(n + 1, dtype=np.int32)
-        begin[1:] = np.cumsum([(p.numel() + CHUNK - 1) // CHUNK for p in params])
-        assert int(begin[-1]) == plan.nchunks, (int(begin[-1]), plan.nchunks)
-        dev = plan.device
-        self.key = tuple(adapt)
-        self.n = n
-        self.chunk_begin = _to_device_async(torch.from_numpy(begin), dev)
-        self.flags = _to_device_async(torch.tensor([int(a) for a in adapt], dtype=torch.int32), dev)
-        self.partials = torch.zeros(2 * max(plan.nchunks, 1), dtype=torch.float32, device=dev)
-        self.norms = torch.zeros((2, max(n, 1)), dtype=torch.float32, device=dev)
-
-
-def _norm_tables(plan, params, adapt):
-    nt = getattr(plan, "norm_tables", None)
-    if nt is None or nt.key != tuple(adapt):
-        nt = plan.norm_tables = _NormTables(plan, params, adapt)
-    return nt
-
-
 def multi_tensor_l2norm(tensors):
     """Per-tensor L2 norms (float32 device tensor of ``len(tensors)``) and their global L2 norm
     (0-d device tensor) of fp32 CUDA tensors, contiguous or channels_last-dense: two launches
@@ -519,18 +725,15 @@ def multi_tensor_l2norm(tensors):
 
 
 class _LayerwiseBase(_FusedBase):
-    """Shared by FusedLARS / FusedLAMB: the adapt flags, the global gradient norm and clip
-    coefficient (one device buffer for the optimizer, combined over the param groups in group
-    order), the norm launches.
+    """Shared by FusedLARS / FusedLAMB: the adapt flags; the global gradient norm, the clip
+    coefficient and the norm launches are ``_FusedBase``'s.
 
     The global norm spans every group, so the native path runs only when every group with
     gradients passes ``_native_ok``; otherwise the whole step runs ``_torch_step``."""
     whole_step_fallback = True
 
     def __init__(self, params, defaults, max_grad_norm, write_bf16_shadow, capturable):
-        super().__init__(params, defaults, write_bf16_shadow, capturable)
-        self.max_grad_norm = float(max_grad_norm)
-        self._glob = None  # device [sum of squares (one double), gnorm, clip]
+        super().__init__(params, defaults, write_bf16_shadow, capturable, max_grad_norm)
 
     def load_state_dict(self, state_dict):
         """torch's; a checkpoint written by ``torch.optim.SGD`` / ``Adam`` has none of the
@@ -547,38 +750,6 @@ class _LayerwiseBase(_FusedBase):
     @staticmethod
     def _adapt(group, p):
         return not (group["exclude_1d"] and p.dim() <= 1)
-
-    def _global(self, device):
-        if self._glob is None or self._glob.device != device:
-            self._glob = torch.zeros(4, dtype=torch.float32, device=device)
-            self._glob[3] = 1.0
-        return self._glob
-
-    def _tables(self, gi, group, params, roles):
-        plan = self._plan(gi, params, roles, params[0].device)
-        return plan, _norm_tables(plan, params, [self._adapt(group, p) for p in params])
-
-    def _sumsq(self, plan, nt, a, b):
-        _call("sumsq_chunks", plan.chunks.data_ptr(), plan.nchunks, plan.ptr(a), plan.ptr(b) if b else None,
-              nt.partials.data_ptr(), self._stream())
-
-    def _finalize(self, nt, nroles, grole, glob, start_zero):
-        _call("norm_finalize", nt.partials.data_ptr(), nt.chunk_begin.data_ptr(), nt.n, nroles, grole,
-              nt.norms.data_ptr(), glob.data_ptr() if glob is not None else None, int(start_zero),
-              self.max_grad_norm, self._stream())
-
-    def _torch_clip(self, work):
-        """The clip coefficient as a 0-d fp32 tensor (no host sync), or None without clipping."""
-        if self.max_grad_norm <= 0:
-            return None
-        sq = [p.grad.double().pow(2).sum() for _, _, params in work for p in params]
-        gnorm = torch.stack([s.to(sq[0].device) for s in sq]).sum().sqrt()
-        return torch.clamp(self.max_grad_norm / (gnorm + 1e-6), max=1.0).float()
-
-    def grad_norm(self):
-        """The global gradient norm of the last native step as a 0-d device tensor (before
-        clipping; no host sync), or None if no native step has run."""
-        return None if self._glob is None else self._glob[2]
 
 
 class FusedLARS(_LayerwiseBase):

@@ -19,7 +19,9 @@ Extra (optional) ``trainer`` keys, all defaulting to reference behaviour:
   hip_graph bool (capture the training step -- DDP all-reduce included -- as one HIP
   graph after a warm-up and replay it; needs a fused optimizer, built capturable),
   ema {decay, warmup, validate "both"|"ema"|"model"} (``optim.ModelEMA``, updated after every
-  optimizer step; absent / null: off), lr_step "epoch"|"iteration" (when the scheduler steps).
+  optimizer step; absent / null: off), lr_step "epoch"|"iteration" (when the scheduler steps),
+  log_grad_norm bool (``grad_norm`` / ``skipped_steps`` of an ``optim.Fused*`` optimizer in the
+  epoch log).
 """
 from __future__ import annotations
 

@@ -34,6 +34,12 @@ MI355X-first changes to the hot loop:
     steps build its tables). ``validate``: ``"both"`` (default) reports ``val_*`` for the trained
     weights and ``val_ema_*`` for the averaged ones, ``"ema"`` / ``"model"`` only one of them;
     ``monitor`` may name ``val_ema_<metric>``. Absent or null, nothing changes;
+  * ``trainer.log_grad_norm`` (default false; needs an optimizer with ``grad_norm()``, i.e.
+    ``optim.Fused*`` with ``max_grad_norm`` or ``skip_nonfinite``): the global gradient norm of
+    every step, eager or replayed, is accumulated on the device the way the loss is -- no
+    per-iteration sync -- and the epoch log gets ``grad_norm`` (the mean of the finite norms,
+    before clipping) and, where the optimizer counts them, ``skipped_steps`` (the steps
+    ``skip_nonfinite`` declined in the epoch);
   * ``trainer.lr_step``: ``"epoch"`` (default, the reference's) or ``"iteration"`` -- the
     scheduler steps after every optimizer step, graph replays included (the host value; a
     capturable optimizer's ``refresh_scalars()`` carries it to the device before each replay).
@@ -147,6 +153,8 @@ class Trainer(BaseTrainer):
         self.lr_step = config["trainer"].get("lr_step", "epoch")
         if self.lr_step not in ("epoch", "iteration"):
             raise ValueError(f'trainer.lr_step must be "epoch" or "iteration", got {self.lr_step!r}')
+        # the optimizer's global gradient norm in the epoch log (trainer.log_grad_norm)
+        self.log_grad_norm = bool(config["trainer"].get("log_grad_norm", False)) and hasattr(optimizer, "grad_norm")
         self.last_throughput = None
         # optional per-phase device timing (HIP events + ROCTx ranges): trainer.profile_phases
         self.phase_timer = PhaseTimer(enabled=bool(config["trainer"].get("profile_phases", False))
@@ -194,6 +202,11 @@ class Trainer(BaseTrainer):
         self.model.train()
         self.train_metrics.reset()
         loss_sum = torch.zeros((), dtype=torch.float32, device=self.device)
+        if self.log_grad_norm:
+            gnorm_sum = torch.zeros((), dtype=torch.float32, device=self.device)
+            gnorm_n = torch.zeros((), dtype=torch.float32, device=self.device)
+            skipped = getattr(self.optimizer, "skipped_steps", None)
+            skipped_at_start = skipped().clone() if skipped is not None else None
         n_iter = 0
         n_images = 0
         warm = min(2, max(0, self.len_epoch - 1))
@@ -225,6 +238,13 @@ class Trainer(BaseTrainer):
                 self.lr_scheduler.step()
 
             loss_sum += loss.detach().float()
+            if self.log_grad_norm:
+                # (a replay rewrites the norm in place: read it behind the step, like the loss)
+                gnorm = self.optimizer.grad_norm()
+                if gnorm is not None:
+                    finite = torch.isfinite(gnorm)
+                    gnorm_sum += torch.where(finite, gnorm, torch.zeros_like(gnorm)).to(self.device)
+                    gnorm_n += finite.to(self.device)
             n_iter += 1
             n_images += data.shape[0]
 
@@ -259,6 +279,11 @@ class Trainer(BaseTrainer):
         # the TB curve got its per-log-step points above: the epoch mean is not written again
         self.train_metrics.update("loss", mean_loss.item(), n=1, write=False)
         log = self.train_metrics.result()
+        if self.log_grad_norm:
+            # the norm is taken from the averaged gradients: the same on every rank
+            log["grad_norm"] = (gnorm_sum / gnorm_n).item() if gnorm_n.item() > 0 else float("nan")
+            if skipped_at_start is not None:
+                log["skipped_steps"] = int((self.optimizer.skipped_steps() - skipped_at_start).item())
         if self.last_throughput is not None:
             log["images_per_sec"] = round(self.last_throughput, 2)
         if self.phase_timer.enabled:
