@@ -38,28 +38,35 @@ namespace {
 constexpr int NT = 256;
 
 // One axis of the bilinear sampler: output coordinate o of n source pixels resized to S.
-// S2 = 2S, inv2S = 1 / 2S. (2S+1) n < 2^31 is checked on the host. (axis_taps_om below is its
-// twin for the erase paths: keep the two in step.)
-__device__ __forceinline__ void axis_taps(int o, int n, int S, int S2, float inv2S, int& i0, int& i1, float& l) {
+// S2 = 2S, inv2S = 1 / 2S. (2S+1) n < 2^31 is checked on the host. The blend weights are
+// l = rem / 2S and om = 1 - l, the latter as one fma (one rounding), spelled out: every path forms
+// it here, so the bits cannot differ between a straight-line path and one behind a per-lane branch.
+struct Axis {
+  int i0, i1;   // the two taps, clamped to the box
+  float l, om;  // the weight of i1 and of i0
+};
+__device__ __forceinline__ Axis axis_taps(int o, int n, int S, int S2, float inv2S) {
   int num = (2 * o + 1) * n - S;
   num = num < 0 ? 0 : num;
   int i = (int)((float)num * inv2S);  // floor(num / 2S) up to +-1: fixed below
   int r = num - i * S2;
   if (r < 0) { --i; r += S2; }
   if (r >= S2) { ++i; r -= S2; }
-  l = (float)r * inv2S;
-  i0 = i < n - 1 ? i : n - 1;
-  i1 = i0 + 1 < n - 1 ? i0 + 1 : n - 1;
+  const int i0 = i < n - 1 ? i : n - 1;
+  return Axis{i0, i0 + 1 < n - 1 ? i0 + 1 : n - 1, (float)r * inv2S, fmaf(-inv2S, (float)r, 1.f)};
 }
 
-// The three bytes of the pixel at byte offset off of an image, in bits 0..23 (R, G, B from the
-// low byte). One unaligned dword load that never leaves the image: bytes [off-1, off+3) for
-// off > 0, bytes [0, 4) for the first pixel (an image has >= 4 bytes, host check).
-__device__ __forceinline__ uint32_t load_rgb(const uint8_t* __restrict__ img, uint32_t off) {
+// The three bytes of the pixel at byte offset off of an image: w >> sh has them in bits 0..23 (R,
+// G, B from the low byte). One unaligned dword load that never leaves the image: bytes
+// [off-1, off+3) for off > 0, bytes [0, 4) for the first pixel (an image has >= 4 bytes, host
+// check). DEFER leaves the shift (0 or 8) to the caller; otherwise it is applied here and sh is 0.
+template <bool DEFER>
+__device__ __forceinline__ uint32_t load_rgb(const uint8_t* __restrict__ img, uint32_t off, uint32_t& sh) {
   const uint32_t back = off > 0 ? 1u : 0u;
   uint32_t w;
   __builtin_memcpy(&w, img + (off - back), 4);
-  return w >> (back * 8);
+  sh = DEFER ? back * 8 : 0u;
+  return DEFER ? w : w >> (back * 8);
 }
 
 struct PixelOut {
@@ -72,24 +79,34 @@ struct Rgb {
 
 struct Taps {
   uint32_t p00, p01, p10, p11;  // load_rgb of the four taps
-  float ly, lx;
+  uint32_t sh;                  // their four shifts, one per byte
+  float ly, lx, omy, omx;       // the weights l and 1 - l of the two axes
 };
 
-__device__ __forceinline__ Taps load_taps(const uint8_t* __restrict__ img, uint32_t row0, uint32_t row1, int ix,
-                                          int ix1, float ly, float lx) {
-  return Taps{load_rgb(img, (row0 + (uint32_t)ix) * 3u), load_rgb(img, (row0 + (uint32_t)ix1) * 3u),
-              load_rgb(img, (row1 + (uint32_t)ix) * 3u), load_rgb(img, (row1 + (uint32_t)ix1) * 3u), ly, lx};
+template <bool DEFER>
+__device__ __forceinline__ Taps load_taps(const uint8_t* __restrict__ img, uint32_t row0, uint32_t row1, const Axis& y,
+                                          const Axis& x) {
+  uint32_t s00, s01, s10, s11;
+  Taps t;
+  t.p00 = load_rgb<DEFER>(img, (row0 + (uint32_t)x.i0) * 3u, s00);
+  t.p01 = load_rgb<DEFER>(img, (row0 + (uint32_t)x.i1) * 3u, s01);
+  t.p10 = load_rgb<DEFER>(img, (row1 + (uint32_t)x.i0) * 3u, s10);
+  t.p11 = load_rgb<DEFER>(img, (row1 + (uint32_t)x.i1) * 3u, s11);
+  t.sh = s00 | (s01 << 8) | (s10 << 16) | (s11 << 24);
+  t.ly = y.l, t.lx = x.l, t.omy = y.om, t.omx = x.om;
+  return t;
 }
 
-// sample()'s blend, operation for operation, without the normalization
+// the bilinear blend, without the normalization
 __device__ __forceinline__ Rgb blend_taps(const Taps& t) {
-  const float ly = t.ly, lx = t.lx;
-  const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
+  const uint32_t p00 = t.p00 >> (t.sh & 0xffu), p01 = t.p01 >> ((t.sh >> 8) & 0xffu);
+  const uint32_t p10 = t.p10 >> ((t.sh >> 16) & 0xffu), p11 = t.p11 >> (t.sh >> 24);
+  const float w00 = t.omy * t.omx, w01 = t.omy * t.lx, w10 = t.ly * t.omx, w11 = t.ly * t.lx;
   Rgb r;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const float a = (float)((t.p00 >> (8 * c)) & 0xffu), b = (float)((t.p01 >> (8 * c)) & 0xffu);
-    const float d = (float)((t.p10 >> (8 * c)) & 0xffu), e = (float)((t.p11 >> (8 * c)) & 0xffu);
+    const float a = (float)((p00 >> (8 * c)) & 0xffu), b = (float)((p01 >> (8 * c)) & 0xffu);
+    const float d = (float)((p10 >> (8 * c)) & 0xffu), e = (float)((p11 >> (8 * c)) & 0xffu);
     r.v[c] = fmaf(w11, e, fmaf(w10, d, fmaf(w01, b, w00 * a)));
   }
   return r;
@@ -104,28 +121,6 @@ __device__ __forceinline__ PixelOut finish(const Rgb& r, float m0, float m1, flo
   return o;
 }
 
-__device__ __forceinline__ PixelOut sample(const uint8_t* __restrict__ img, uint32_t row0, uint32_t row1, int ix,
-                                           int ix1, float ly, float lx, float m0, float m1, float m2, float s0,
-                                           float s1, float s2) {
-  const uint32_t p00 = load_rgb(img, (row0 + (uint32_t)ix) * 3u);
-  const uint32_t p01 = load_rgb(img, (row0 + (uint32_t)ix1) * 3u);
-  const uint32_t p10 = load_rgb(img, (row1 + (uint32_t)ix) * 3u);
-  const uint32_t p11 = load_rgb(img, (row1 + (uint32_t)ix1) * 3u);
-  const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
-  float v[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float a = (float)((p00 >> (8 * c)) & 0xffu), b = (float)((p01 >> (8 * c)) & 0xffu);
-    const float d = (float)((p10 >> (8 * c)) & 0xffu), e = (float)((p11 >> (8 * c)) & 0xffu);
-    v[c] = fmaf(w11, e, fmaf(w10, d, fmaf(w01, b, w00 * a)));
-  }
-  constexpr float K = 1.f / 255.f;
-  PixelOut o;
-  o.lo = pack2bf((fmaf(v[0], K, -m0)) * s0, (fmaf(v[1], K, -m1)) * s1);
-  o.hi = pack2bf((fmaf(v[2], K, -m2)) * s2, 0.f);
-  return o;
-}
-
 // One augmented view: an image and its crop box. Wave-uniform as loaded; a CutMix lane holds its
 // own choice of two.
 struct View {
@@ -133,15 +128,25 @@ struct View {
   int y0, x0, h, w, flip;
 };
 
+__device__ __forceinline__ View select_view(bool in, const View& par, const View& own) {
+  return View{in ? par.img : own.img, in ? par.y0 : own.y0, in ? par.x0 : own.x0,
+              in ? par.h : own.h,     in ? par.w : own.w,   in ? par.flip : own.flip};
+}
+
 // The loaded taps of output pixel (oy, ox) of view v, formed from scratch (CutMix: the lane's
-// two pixels may read different views).
-__device__ __forceinline__ Taps view_taps(const View& v, int oy, int ox, int Ws, int S, int S2, float inv2S) {
-  int iy, iy1, ix, ix1;
-  float ly, lx;
-  axis_taps(oy, v.h, S, S2, inv2S, iy, iy1, ly);
-  axis_taps(v.flip ? S - 1 - ox : ox, v.w, S, S2, inv2S, ix, ix1, lx);
-  const uint32_t row0 = (uint32_t)((v.y0 + iy) * Ws + v.x0), row1 = (uint32_t)((v.y0 + iy1) * Ws + v.x0);
-  return load_taps(v.img, row0, row1, ix, ix1, ly, lx);
+// two pixels may read different views). PREDICATED (the ERASE paths): only a lane that samples
+// (on) issues loads, and their shifts are left to blend_taps, behind the caller's pin -- inside the
+// per-lane branch a shift would wait for its load there, and the other pixel's loads would issue
+// behind that wait. Otherwise on is ignored and the loads are shifted at once.
+template <bool PREDICATED>
+__device__ __forceinline__ Taps view_taps(bool on, const View& v, int oy, int ox, int Ws, int S, int S2, float inv2S) {
+  Taps t{};
+  if (!PREDICATED || on) {
+    const Axis y = axis_taps(oy, v.h, S, S2, inv2S), x = axis_taps(v.flip ? S - 1 - ox : ox, v.w, S, S2, inv2S);
+    t = load_taps<PREDICATED>(v.img, (uint32_t)((v.y0 + y.i0) * Ws + v.x0), (uint32_t)((v.y0 + y.i1) * Ws + v.x0),
+                              y, x);
+  }
+  return t;
 }
 
 // Mixup / CutMix operands of output b (MIX kernels): the partner's augmented view -- its gather
@@ -155,9 +160,10 @@ struct MixArgs {
 };
 struct NoMix {};
 
-// The kernel's store, for the mixing paths: 4 bf16 (8 bytes) per padded pixel, 64-bit pixel index
-__device__ __forceinline__ void store_pair(u16* __restrict__ out, long pix, bool pair, PixelOut a, PixelOut c) {
-  uint2* o = reinterpret_cast<uint2*>(out) + pix;
+// The kernel's store of the pair at (b, oy, ox0): 4 bf16 (8 bytes) per padded pixel, 64-bit pixel index
+__device__ __forceinline__ void store_pair(u16* __restrict__ out, long b, int S, int oy, int ox0, bool pair, PixelOut a,
+                                           PixelOut c) {
+  uint2* o = reinterpret_cast<uint2*>(out) + ((b * S + oy) * S + ox0);
   if (pair) {
     // 8-byte aligned always, 16-byte aligned for even S
     typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
@@ -201,81 +207,33 @@ __device__ __forceinline__ PixelOut erase_fill(uint32_t key, uint32_t q, int mod
   return PixelOut{pack2bf(z[0], z[1]), pack2bf(z[2], 0.f)};
 }
 
-// The erase paths sample under a per-lane branch, and must still give the bits of the straight-line
-// paths. There the compiler contracts the blend weight l = r * inv2S into 1 - l, i.e. forms
-// fma(-inv2S, r, 1) with one rounding (every 1 - l of the non-erase kernels' ISA is that v_fma);
-// across a branch it would round l first. So these twins of axis_taps / view_taps / blend_taps
-// spell that fma out and carry 1 - l beside l.
-struct TapsOm {
-  Taps t;          // p00..p11 as loaded: blend_taps_om shifts them, behind the caller's pin
-  float omy, omx;  // 1 - ly, 1 - lx
-  uint32_t sh;     // load_rgb's four shifts (0 or 8), one per byte
-};
-
-__device__ __forceinline__ void axis_taps_om(int o, int n, int S, int S2, float inv2S, int& i0, int& i1, float& l,
-                                             float& om) {
-  int num = (2 * o + 1) * n - S;
-  num = num < 0 ? 0 : num;
-  int i = (int)((float)num * inv2S);
-  int r = num - i * S2;
-  if (r < 0) { --i; r += S2; }
-  if (r >= S2) { ++i; r -= S2; }
-  l = (float)r * inv2S;
-  om = fmaf(-inv2S, (float)r, 1.f);
-  i0 = i < n - 1 ? i : n - 1;
-  i1 = i0 + 1 < n - 1 ? i0 + 1 : n - 1;
-}
-
-// load_rgb without its shift: inside a branch the shift would wait for the load there, and the
-// other pixel's loads would issue behind that wait
-__device__ __forceinline__ uint32_t load_rgb_raw(const uint8_t* __restrict__ img, uint32_t off, uint32_t& sh) {
-  const uint32_t back = off > 0 ? 1u : 0u;
-  uint32_t w;
-  __builtin_memcpy(&w, img + (off - back), 4);
-  sh = back * 8;
-  return w;
-}
-
-// view_taps for a lane that samples (on); any other lane issues no load
-__device__ __forceinline__ TapsOm view_taps_om(bool on, const View& v, int oy, int ox, int Ws, int S, int S2,
-                                               float inv2S) {
-  TapsOm r{};
-  if (on) {
-    int iy, iy1, ix, ix1;
-    axis_taps_om(oy, v.h, S, S2, inv2S, iy, iy1, r.t.ly, r.omy);
-    axis_taps_om(v.flip ? S - 1 - ox : ox, v.w, S, S2, inv2S, ix, ix1, r.t.lx, r.omx);
-    const uint32_t row0 = (uint32_t)((v.y0 + iy) * Ws + v.x0), row1 = (uint32_t)((v.y0 + iy1) * Ws + v.x0);
-    uint32_t s00, s01, s10, s11;
-    r.t.p00 = load_rgb_raw(v.img, (row0 + (uint32_t)ix) * 3u, s00);
-    r.t.p01 = load_rgb_raw(v.img, (row0 + (uint32_t)ix1) * 3u, s01);
-    r.t.p10 = load_rgb_raw(v.img, (row1 + (uint32_t)ix) * 3u, s10);
-    r.t.p11 = load_rgb_raw(v.img, (row1 + (uint32_t)ix1) * 3u, s11);
-    r.sh = s00 | (s01 << 8) | (s10 << 16) | (s11 << 24);
-  }
-  return r;
-}
-
-__device__ __forceinline__ Rgb blend_taps_om(const TapsOm& q) {
-  const Taps& t = q.t;
-  const uint32_t p00 = t.p00 >> (q.sh & 0xffu), p01 = t.p01 >> ((q.sh >> 8) & 0xffu);
-  const uint32_t p10 = t.p10 >> ((q.sh >> 16) & 0xffu), p11 = t.p11 >> (q.sh >> 24);
-  const float w00 = q.omy * q.omx, w01 = q.omy * t.lx, w10 = t.ly * q.omx, w11 = t.ly * t.lx;
-  Rgb r;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float a = (float)((p00 >> (8 * c)) & 0xffu), b = (float)((p01 >> (8 * c)) & 0xffu);
-    const float d = (float)((p10 >> (8 * c)) & 0xffu), e = (float)((p11 >> (8 * c)) & 0xffu);
-    r.v[c] = fmaf(w11, e, fmaf(w10, d, fmaf(w01, b, w00 * a)));
-  }
-  return r;
-}
-
 // Mixup of one pixel on the fp32 0..255 values: the partner's inside the rectangle
 __device__ __forceinline__ Rgb mixup_rgb(const Rgb& own, const Rgb& par, bool in, float wo, float wp) {
   Rgb r;
 #pragma unroll
   for (int c = 0; c < 3; ++c) r.v[c] = in ? par.v[c] : fmaf(wo, own.v[c], wp * par.v[c]);
   return r;
+}
+
+// The mix operands of image b as a lane uses them: its own view and the partner's, whether its
+// two pixels lie inside the cut rectangle, the weight of the own pixels outside it, and whether
+// anything mixes at all (wave-uniform).
+struct MixOps {
+  View own, par;
+  bool ina, inc;
+  float wo;
+  bool any;
+};
+__device__ __forceinline__ MixOps load_mix(const MixArgs& mix, const uint8_t* __restrict__ src, long img_bytes,
+                                           uint32_t b, const View& own, int oy, int ox0, int ox1) {
+  const int* rc = mix.rect + (long)b * 4;
+  const int ry0 = rc[0], rx0 = rc[1], ry1 = rc[2], rx1 = rc[3];
+  const float wo = mix.w_own[b];
+  const int* pb = mix.pbox + (long)b * 5;
+  const View par{src + (long)mix.pidx[b] * img_bytes, pb[0], pb[1], pb[2], pb[3], pb[4]};
+  const bool iny = oy >= ry0 && oy < ry1;
+  return MixOps{own, par, iny && ox0 >= rx0 && ox0 < rx1, iny && ox1 >= rx0 && ox1 < rx1, wo,
+                wo != 1.f || (ry0 < ry1 && rx0 < rx1)};
 }
 
 // grid.x = B * nblk: workgroup (b, k) covers pixel pairs [k NT, (k+1) NT) of image b's S * P
@@ -293,7 +251,7 @@ __device__ __forceinline__ Rgb mixup_rgb(const Rgb& own, const Rgb& par, bool in
 // ERASE: the R rectangles of image b are wave-uniform (scalar loads). All empty: fall through to
 // the code above and below, as the non-erase instantiation runs it. Otherwise the rectangle test
 // is per lane and per pixel; an erased pixel (and the dropped second pixel of the odd-S tail)
-// issues no load, every other pixel samples as its mixing case says, one view_taps_om per pixel.
+// issues no load, every other pixel samples as its mixing case says, one view_taps per pixel.
 template <bool MIX, bool ERASE, class Mix>
 __global__ void __launch_bounds__(NT)
 crop_resize_norm_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ idx, const int* __restrict__ box,
@@ -303,9 +261,9 @@ crop_resize_norm_kernel(const uint8_t* __restrict__ src, const int64_t* __restri
   const uint32_t p = (blockIdx.x - b * nblk) * NT + threadIdx.x;
   if (p >= (uint32_t)(S * P)) return;
   const int* bx = box + (long)b * 5;
-  const int y0 = bx[0], x0 = bx[1], h = bx[2], w = bx[3], flip = bx[4];
   const long im = idx ? (long)idx[b] : (long)b;
-  const uint8_t* img = src + im * img_bytes;  // 64-bit image base; offsets inside an image are 32-bit
+  // 64-bit image base; offsets inside an image are 32-bit
+  const View own{src + im * img_bytes, bx[0], bx[1], bx[2], bx[3], bx[4]};
 
   const int oy = (int)fdiv(p, dP);
   const int ox0 = 2 * ((int)p - oy * P);
@@ -339,119 +297,72 @@ crop_resize_norm_kernel(const uint8_t* __restrict__ src, const int64_t* __restri
       const int mode = era->mode;
       const uint32_t q = (uint32_t)(oy * S + ox0);
       const bool sa = !ea, sc = pair && !ec;  // the pixels that sample
-      const long pix = ((long)b * S + oy) * S + ox0;
-      const View own{img, y0, x0, h, w, flip};
       PixelOut a{0u, 0u}, c{0u, 0u};
-      bool mixup = false;
-      View va = own, vc = own;
-      if constexpr (MIX) {
-        const int* rc = mix.rect + (long)b * 4;
-        const int ry0 = rc[0], rx0 = rc[1], ry1 = rc[2], rx1 = rc[3];
-        const float wo = mix.w_own[b];
-        const int* pb = mix.pbox + (long)b * 5;
-        const View par{src + (long)mix.pidx[b] * img_bytes, pb[0], pb[1], pb[2], pb[3], pb[4]};
-        const bool iny = oy >= ry0 && oy < ry1;
-        const bool ina = iny && ox0 >= rx0 && ox0 < rx1, inc = iny && ox1 >= rx0 && ox1 < rx1;
-        mixup = wo != 1.f;
-        if (mixup) {
-          TapsOm oa = view_taps_om(sa, own, oy, ox0, Ws, S, S2, inv2S), oc = view_taps_om(sc, own, oy, ox1, Ws, S, S2, inv2S);
-          TapsOm qa = view_taps_om(sa, par, oy, ox0, Ws, S, S2, inv2S), qc = view_taps_om(sc, par, oy, ox1, Ws, S, S2, inv2S);
-          asm volatile("" : "+v"(oa.t.p00), "+v"(oa.t.p01), "+v"(oa.t.p10), "+v"(oa.t.p11), "+v"(oc.t.p00),
-                            "+v"(oc.t.p01), "+v"(oc.t.p10), "+v"(oc.t.p11), "+v"(qa.t.p00), "+v"(qa.t.p01),
-                            "+v"(qa.t.p10), "+v"(qa.t.p11), "+v"(qc.t.p00), "+v"(qc.t.p01), "+v"(qc.t.p10),
-                            "+v"(qc.t.p11));
-          const float wp = 1.f - wo;
-          if (sa) a = finish(mixup_rgb(blend_taps_om(oa), blend_taps_om(qa), ina, wo, wp), m0, m1, m2, s0, s1, s2);
-          if (sc) c = finish(mixup_rgb(blend_taps_om(oc), blend_taps_om(qc), inc, wo, wp), m0, m1, m2, s0, s1, s2);
-        } else {
-          va = View{ina ? par.img : own.img, ina ? par.y0 : own.y0, ina ? par.x0 : own.x0,
-                    ina ? par.h : own.h,     ina ? par.w : own.w,   ina ? par.flip : own.flip};
-          vc = View{inc ? par.img : own.img, inc ? par.y0 : own.y0, inc ? par.x0 : own.x0,
-                    inc ? par.h : own.h,     inc ? par.w : own.w,   inc ? par.flip : own.flip};
-        }
-      }
-      if (!mixup) {
-        TapsOm ta = view_taps_om(sa, va, oy, ox0, Ws, S, S2, inv2S), tc = view_taps_om(sc, vc, oy, ox1, Ws, S, S2, inv2S);
+      MixOps m{own, own, false, false, 1.f, false};
+      if constexpr (MIX) m = load_mix(mix, src, img_bytes, b, own, oy, ox0, ox1);
+      if (m.wo != 1.f) {
+        Taps oa = view_taps<true>(sa, own, oy, ox0, Ws, S, S2, inv2S), oc = view_taps<true>(sc, own, oy, ox1, Ws, S, S2, inv2S);
+        Taps qa = view_taps<true>(sa, m.par, oy, ox0, Ws, S, S2, inv2S), qc = view_taps<true>(sc, m.par, oy, ox1, Ws, S, S2, inv2S);
+        asm volatile("" : "+v"(oa.p00), "+v"(oa.p01), "+v"(oa.p10), "+v"(oa.p11), "+v"(oc.p00), "+v"(oc.p01),
+                          "+v"(oc.p10), "+v"(oc.p11), "+v"(qa.p00), "+v"(qa.p01), "+v"(qa.p10), "+v"(qa.p11),
+                          "+v"(qc.p00), "+v"(qc.p01), "+v"(qc.p10), "+v"(qc.p11));
+        const float wp = 1.f - m.wo;
+        if (sa) a = finish(mixup_rgb(blend_taps(oa), blend_taps(qa), m.ina, m.wo, wp), m0, m1, m2, s0, s1, s2);
+        if (sc) c = finish(mixup_rgb(blend_taps(oc), blend_taps(qc), m.inc, m.wo, wp), m0, m1, m2, s0, s1, s2);
+      } else {
+        Taps ta = view_taps<true>(sa, select_view(m.ina, m.par, own), oy, ox0, Ws, S, S2, inv2S);
+        Taps tc = view_taps<true>(sc, select_view(m.inc, m.par, own), oy, ox1, Ws, S, S2, inv2S);
         // every load issued before the first use (the pins below, for the same reason)
-        asm volatile("" : "+v"(ta.t.p00), "+v"(ta.t.p01), "+v"(ta.t.p10), "+v"(ta.t.p11), "+v"(tc.t.p00),
-                          "+v"(tc.t.p01), "+v"(tc.t.p10), "+v"(tc.t.p11));
-        if (sa) a = finish(blend_taps_om(ta), m0, m1, m2, s0, s1, s2);
-        if (sc) c = finish(blend_taps_om(tc), m0, m1, m2, s0, s1, s2);
+        asm volatile("" : "+v"(ta.p00), "+v"(ta.p01), "+v"(ta.p10), "+v"(ta.p11), "+v"(tc.p00), "+v"(tc.p01),
+                          "+v"(tc.p10), "+v"(tc.p11));
+        if (sa) a = finish(blend_taps(ta), m0, m1, m2, s0, s1, s2);
+        if (sc) c = finish(blend_taps(tc), m0, m1, m2, s0, s1, s2);
       }
       if (ea) a = erase_fill(key, q, mode);
       if (pair && ec) c = erase_fill(key, q + 1u, mode);
-      store_pair(out, pix, pair, a, c);
+      store_pair(out, b, S, oy, ox0, pair, a, c);
       return;
     }
   }
 
   if constexpr (MIX) {
-    const int* rc = mix.rect + (long)b * 4;
-    const int ry0 = rc[0], rx0 = rc[1], ry1 = rc[2], rx1 = rc[3];
-    const float wo = mix.w_own[b];
-    if (wo != 1.f || (ry0 < ry1 && rx0 < rx1)) {
-      const int* pb = mix.pbox + (long)b * 5;
-      const View own{img, y0, x0, h, w, flip};
-      const View par{src + (long)mix.pidx[b] * img_bytes, pb[0], pb[1], pb[2], pb[3], pb[4]};
-      const long pix = ((long)b * S + oy) * S + ox0;
-      const bool iny = oy >= ry0 && oy < ry1;
-      const bool ina = iny && ox0 >= rx0 && ox0 < rx1, inc = iny && ox1 >= rx0 && ox1 < rx1;
-      if (wo == 1.f) {
-        const View va{ina ? par.img : own.img, ina ? par.y0 : own.y0, ina ? par.x0 : own.x0,
-                      ina ? par.h : own.h,     ina ? par.w : own.w,   ina ? par.flip : own.flip};
-        const View vc{inc ? par.img : own.img, inc ? par.y0 : own.y0, inc ? par.x0 : own.x0,
-                      inc ? par.h : own.h,     inc ? par.w : own.w,   inc ? par.flip : own.flip};
-        Taps ta = view_taps(va, oy, ox0, Ws, S, S2, inv2S), tc = view_taps(vc, oy, ox1, Ws, S, S2, inv2S);
+    const MixOps m = load_mix(mix, src, img_bytes, b, own, oy, ox0, ox1);
+    if (m.any) {
+      if (m.wo == 1.f) {
+        Taps ta = view_taps<false>(true, select_view(m.ina, m.par, own), oy, ox0, Ws, S, S2, inv2S);
+        Taps tc = view_taps<false>(true, select_view(m.inc, m.par, own), oy, ox1, Ws, S, S2, inv2S);
         // every load issued before the first use (the pin below, for the same reason)
         asm volatile("" : "+v"(ta.p00), "+v"(ta.p01), "+v"(ta.p10), "+v"(ta.p11), "+v"(tc.p00), "+v"(tc.p01),
                           "+v"(tc.p10), "+v"(tc.p11));
-        store_pair(out, pix, pair, finish(blend_taps(ta), m0, m1, m2, s0, s1, s2),
+        store_pair(out, b, S, oy, ox0, pair, finish(blend_taps(ta), m0, m1, m2, s0, s1, s2),
                    finish(blend_taps(tc), m0, m1, m2, s0, s1, s2));
         return;
       }
       // Mixup: both pixels' taps of both views, 16 loads in flight
-      Taps oa = view_taps(own, oy, ox0, Ws, S, S2, inv2S), oc = view_taps(own, oy, ox1, Ws, S, S2, inv2S);
-      Taps qa = view_taps(par, oy, ox0, Ws, S, S2, inv2S), qc = view_taps(par, oy, ox1, Ws, S, S2, inv2S);
+      Taps oa = view_taps<false>(true, own, oy, ox0, Ws, S, S2, inv2S), oc = view_taps<false>(true, own, oy, ox1, Ws, S, S2, inv2S);
+      Taps qa = view_taps<false>(true, m.par, oy, ox0, Ws, S, S2, inv2S), qc = view_taps<false>(true, m.par, oy, ox1, Ws, S, S2, inv2S);
       asm volatile("" : "+v"(oa.p00), "+v"(oa.p01), "+v"(oa.p10), "+v"(oa.p11), "+v"(oc.p00), "+v"(oc.p01),
                         "+v"(oc.p10), "+v"(oc.p11), "+v"(qa.p00), "+v"(qa.p01), "+v"(qa.p10), "+v"(qa.p11),
                         "+v"(qc.p00), "+v"(qc.p01), "+v"(qc.p10), "+v"(qc.p11));
       const Rgb ova = blend_taps(oa), ovc = blend_taps(oc), pva = blend_taps(qa), pvc = blend_taps(qc);
-      const float wp = 1.f - wo;
-      Rgb ra, rc2;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        ra.v[c] = ina ? pva.v[c] : fmaf(wo, ova.v[c], wp * pva.v[c]);
-        rc2.v[c] = inc ? pvc.v[c] : fmaf(wo, ovc.v[c], wp * pvc.v[c]);
-      }
-      store_pair(out, pix, pair, finish(ra, m0, m1, m2, s0, s1, s2), finish(rc2, m0, m1, m2, s0, s1, s2));
+      const float wp = 1.f - m.wo;
+      store_pair(out, b, S, oy, ox0, pair, finish(mixup_rgb(ova, pva, m.ina, m.wo, wp), m0, m1, m2, s0, s1, s2),
+                 finish(mixup_rgb(ovc, pvc, m.inc, m.wo, wp), m0, m1, m2, s0, s1, s2));
       return;
     }
   }
 
-  int iy, iy1;
-  float ly;
-  axis_taps(oy, h, S, S2, inv2S, iy, iy1, ly);
-  const uint32_t row0 = (uint32_t)((y0 + iy) * Ws + x0), row1 = (uint32_t)((y0 + iy1) * Ws + x0);
-
-  int ixa, ixa1, ixb, ixb1;
-  float lxa, lxb;
-  axis_taps(flip ? S - 1 - ox0 : ox0, w, S, S2, inv2S, ixa, ixa1, lxa);
-  axis_taps(flip ? S - 1 - ox1 : ox1, w, S, S2, inv2S, ixb, ixb1, lxb);
-  const PixelOut a = sample(img, row0, row1, ixa, ixa1, ly, lxa, m0, m1, m2, s0, s1, s2);
-  PixelOut c = sample(img, row0, row1, ixb, ixb1, ly, lxb, m0, m1, m2, s0, s1, s2);
+  // the plain path: one row computation shared by the lane's two pixels
+  const Axis y = axis_taps(oy, own.h, S, S2, inv2S);
+  const uint32_t row0 = (uint32_t)((own.y0 + y.i0) * Ws + own.x0), row1 = (uint32_t)((own.y0 + y.i1) * Ws + own.x0);
+  const Axis xa = axis_taps(own.flip ? S - 1 - ox0 : ox0, own.w, S, S2, inv2S);
+  const Axis xc = axis_taps(own.flip ? S - 1 - ox1 : ox1, own.w, S, S2, inv2S);
+  const PixelOut a = finish(blend_taps(load_taps<false>(own.img, row0, row1, y, xa)), m0, m1, m2, s0, s1, s2);
+  PixelOut c = finish(blend_taps(load_taps<false>(own.img, row0, row1, y, xc)), m0, m1, m2, s0, s1, s2);
   // pin the second pixel here: left alone, the compiler sinks its four loads into the `pair`
-  // branch below, behind the first pixel's waits (half the loads in flight per lane)
+  // branch of the store, behind the first pixel's waits (half the loads in flight per lane)
   asm volatile("" : "+v"(c.lo), "+v"(c.hi));
-
-  // 4 bf16 (8 bytes) per padded pixel; 64-bit pixel index
-  uint2* o = reinterpret_cast<uint2*>(out) + (((long)b * S + oy) * S + ox0);
-  if (pair) {
-    // 8-byte aligned always, 16-byte aligned for even S
-    typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
-    *reinterpret_cast<u32x4_a8*>(o) = u32x4_a8{a.lo, a.hi, c.lo, c.hi};
-  } else {
-    *o = uint2{a.lo, a.hi};
-  }
+  store_pair(out, b, S, oy, ox0, pair, a, c);
 }
 
 template <bool MIX, bool ERASE, class Mix>

@@ -148,14 +148,22 @@ _TRIES = 10
 _DRAWS = 4 * _TRIES + 1  # (area, ratio, y, x) per try, then the flip
 
 
-def _uniforms(indices, epoch, seed) -> torch.Tensor:
-    """float64 [B, _DRAWS] in [0, 1): draw j of sample i is a hash of (seed, epoch, i, j)."""
+def _sample_state(indices, epoch, seed) -> torch.Tensor:
+    """uint32 (in int64) [B]: the crop-box stream's state of each sample, a hash of (seed, epoch, i)."""
     idx = torch.as_tensor(indices, dtype=torch.int64).reshape(-1)
     s = _hash32(((idx & _M32) * 0x9E3779B9 & _M32) ^ (int(seed) & _M32))
-    s = _hash32(s ^ ((int(epoch) & _M32) * 0x85EBCA6B & _M32) ^ ((idx >> 32) & _M32))
-    j = torch.arange(1, _DRAWS + 1, dtype=torch.int64)
-    h = _hash32(((j * 0xC2B2AE35) & _M32)[None, :] ^ s[:, None])
+    return _hash32(s ^ ((int(epoch) & _M32) * 0x85EBCA6B & _M32) ^ ((idx >> 32) & _M32))
+
+
+def _draws(state, j) -> torch.Tensor:
+    """float64 [B, len(j)] in [0, 1): draws ``j`` (int64, from 1) of the streams with ``state`` [B]."""
+    h = _hash32(((j * 0xC2B2AE35) & _M32)[None, :] ^ state[:, None])
     return (h >> 8).to(torch.float64) / 16777216.0
+
+
+def _uniforms(indices, epoch, seed) -> torch.Tensor:
+    """float64 [B, _DRAWS] in [0, 1): draw j of sample i is a hash of (seed, epoch, i, j)."""
+    return _draws(_sample_state(indices, epoch, seed), torch.arange(1, _DRAWS + 1, dtype=torch.int64))
 
 
 def random_resized_crop_boxes(indices, epoch, seed, Hs, Ws, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3),
@@ -372,11 +380,8 @@ def check_erase_args(re_prob, re_mode, re_count, re_area, re_aspect):
 
 def _erase_state(indices, epoch, seed) -> torch.Tensor:
     """uint32 (in int64) [B]: the erase stream's state of each sample -- the crop-box stream's
-    state of :func:`_uniforms`, hashed once more with a salt."""
-    idx = torch.as_tensor(indices, dtype=torch.int64).reshape(-1)
-    s = _hash32(((idx & _M32) * 0x9E3779B9 & _M32) ^ (int(seed) & _M32))
-    s = _hash32(s ^ ((int(epoch) & _M32) * 0x85EBCA6B & _M32) ^ ((idx >> 32) & _M32))
-    return _hash32(s ^ _ERASE_SALT)
+    state (:func:`_sample_state`), hashed once more with a salt."""
+    return _hash32(_sample_state(indices, epoch, seed) ^ _ERASE_SALT)
 
 
 def erase_keys(indices, epoch, seed) -> torch.Tensor:
@@ -402,8 +407,7 @@ def random_erasing_rects(indices, epoch, seed, S, re_prob=0.25, re_count=1, re_a
         raise ValueError("random_erasing_rects needs S >= 1")
     s = _erase_state(indices, epoch, seed)
     B = s.shape[0]
-    j = torch.arange(1, 2 + 4 * _TRIES * R, dtype=torch.int64)
-    u = (_hash32(((j * 0xC2B2AE35) & _M32)[None, :] ^ s[:, None]) >> 8).to(torch.float64) / 16777216.0
+    u = _draws(s, torch.arange(1, 2 + 4 * _TRIES * R, dtype=torch.int64))
     erased = u[:, 0] < float(re_prob)
     t = u[:, 1:].reshape(B, R, _TRIES, 4)
     area = S * S * (float(re_area[0]) + t[..., 0] * (float(re_area[1]) - float(re_area[0]))) / R
@@ -486,6 +490,35 @@ def crop_resize_normalize_torch(images, box, S, mean, std, dtype=torch.float32):
             r = r.flip(3)
         out.append((r / 255.0 - m) / s)
     return torch.cat(out).to(dtype)
+
+
+# ----------------------------------------------------------------------------- parameter block
+def _param_layout(B, mixing, R):
+    """The pinned parameter block of a batch of ``B`` in int32 words: field name -> (word offset,
+    word count, dtype, shape). The samples' gather indices, labels and boxes; with ``mixing`` their
+    partners' (``pidx`` / ``plabels`` / ``pbox``), the cut rectangles, ``w_own`` and ``lam``; with
+    ``R`` > 0 erase rectangles per sample, those and one key per sample behind everything else. The
+    int64 vectors come first, so they are 8-byte aligned for any ``B``."""
+    fields = [("kidx", torch.int64, (B,)), ("labels", torch.int64, (B,))]
+    if mixing:
+        fields += [("pidx", torch.int64, (B,)), ("plabels", torch.int64, (B,))]
+    fields.append(("box", torch.int32, (B, 5)))
+    if mixing:
+        fields += [("pbox", torch.int32, (B, 5)), ("rect", torch.int32, (B, 4)), ("w_own", torch.float32, (B,)),
+                   ("lam", torch.float32, (B,))]
+    if R:
+        fields += [("erect", torch.int32, (B, R, 4)), ("ekey", torch.int32, (B,))]
+    layout, off = {}, 0
+    for name, dtype, shape in fields:
+        words = math.prod(shape) * (2 if dtype == torch.int64 else 1)
+        layout[name] = (off, words, dtype, shape)
+        off += words
+    return layout
+
+
+def _block_views(buf, layout):
+    """The fields of ``layout`` as views into the int32 block ``buf``."""
+    return {name: buf[off:off + n].view(dtype).view(shape) for name, (off, n, dtype, shape) in layout.items()}
 
 
 # ----------------------------------------------------------------------------- loader
@@ -651,93 +684,40 @@ class PackedImageLoader:
             yield x.to(self.dtype).contiguous(memory_format=fmt).to(self.device), target
 
     # ------------------------------------------------------------------ native paths
-    @staticmethod
-    def _erase_words(erase, B):
-        """int32 words the erase parameters add to a batch's pinned buffer: the rectangles and one key
-        per sample, behind everything else (the int64 vectors stay in front, 8-byte aligned)."""
-        return 0 if erase is None else (4 * erase[0].shape[1] + 1) * B
-
-    @staticmethod
-    def _put_erase(host, off, erase):
-        """Write ``erase`` = (rects, keys) into the pinned words ``host[off:]``."""
-        rects, keys = erase
-        B, R = rects.shape[:2]
-        host[off:off + 4 * R * B].view(B, R, 4).copy_(rects)
-        host[off + 4 * R * B:off + (4 * R + 1) * B].copy_(u32_bits(keys))
-
-    @staticmethod
-    def _erase_views(dev, off, erase):
-        """The device views ``(erect, ekey)`` of what :meth:`_put_erase` wrote."""
-        B, R = erase[0].shape[:2]
-        return dev[off:off + 4 * R * B].view(B, R, 4), dev[off + 4 * R * B:off + (4 * R + 1) * B]
-
-    def _upload_params(self, kidx, labels, box, erase=None):
-        """One small H2D copy: kernel gather indices, labels (int64 [B] each) and boxes (int32
-        [B, 5]) in one pinned buffer -- with ``erase``, its rectangles and keys behind them.
-        Returns the three device views and, with ``erase``, the pair ``(erect, ekey)``."""
-        B = len(kidx)
-        host = torch.empty(9 * B + self._erase_words(erase, B), dtype=torch.int32, pin_memory=True)
-        host[:2 * B].view(torch.int64).copy_(torch.from_numpy(np.ascontiguousarray(kidx, dtype=np.int64)))
-        host[2 * B:4 * B].view(torch.int64).copy_(torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int64)))
-        host[4 * B:9 * B].view(B, 5).copy_(box)
-        if erase is not None:
-            self._put_erase(host, 9 * B, erase)
-        dev = host.to(self.device, non_blocking=True)
-        views = dev[:2 * B].view(torch.int64), dev[2 * B:4 * B].view(torch.int64), dev[4 * B:9 * B].view(B, 5)
-        return views if erase is None else views + (self._erase_views(dev, 9 * B, erase),)
-
-    def _upload_mixed(self, kidx, labels, box, mix, erase=None):
-        """:meth:`_upload_params` of a mixed batch, still one pinned buffer and one H2D copy: the
-        gather indices, labels and boxes of the samples and of their partners (``kidx[partner]``:
-        in staged mode the partner is read from the same staging slot), the rectangles, ``w_own``
-        and ``lam`` -- with ``erase``, its rectangles and keys behind them. Returns ``(kidx, box,
-        pidx, pbox, rect, w_own)``, the MixedTarget and, with ``erase``, the pair ``(erect, ekey)``."""
-        partner, w_own, rect, lam = mix
-        B = len(kidx)
+    def _upload(self, kidx, labels, box, mix, erase):
+        """One small H2D copy of one pinned buffer (:func:`_param_layout`): the kernel gather indices,
+        labels and boxes; of a mixed batch also those of the partners (``kidx[partner]``: in staged
+        mode the partner is read from the same staging slot), the rectangles, ``w_own`` and ``lam``;
+        with ``erase`` its rectangles and keys. Returns the target (the labels or a MixedTarget) and
+        the device views ``(kidx, box, mixed or None, erased or None)``, ``mixed = (pidx, pbox, rect,
+        w_own)`` and ``erased = (erect, ekey)``."""
         kidx = torch.from_numpy(np.ascontiguousarray(kidx, dtype=np.int64))
         labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int64))
-        host = torch.empty(24 * B + self._erase_words(erase, B), dtype=torch.int32, pin_memory=True)
-        i64 = host[:8 * B].view(torch.int64).view(4, B)  # the int64 vectors first: 8-byte aligned for any B
-        i64[0], i64[1], i64[2], i64[3] = kidx, labels, kidx[partner], labels[partner]
-        host[8 * B:13 * B].view(B, 5).copy_(box)
-        host[13 * B:18 * B].view(B, 5).copy_(box[partner])
-        host[18 * B:22 * B].view(B, 4).copy_(rect)
-        host[22 * B:23 * B].view(torch.float32).copy_(w_own)
-        host[23 * B:24 * B].view(torch.float32).copy_(lam)
+        vals = {"kidx": kidx, "labels": labels, "box": box}
+        if mix is not None:
+            partner, w_own, rect, lam = mix
+            vals.update(pidx=kidx[partner], plabels=labels[partner], pbox=box[partner], rect=rect, w_own=w_own, lam=lam)
         if erase is not None:
-            self._put_erase(host, 24 * B, erase)
-        dev = host.to(self.device, non_blocking=True)
-        d64 = dev[:8 * B].view(torch.int64).view(4, B)
-        args = (d64[0], dev[8 * B:13 * B].view(B, 5), d64[2], dev[13 * B:18 * B].view(B, 5),
-                dev[18 * B:22 * B].view(B, 4), dev[22 * B:23 * B].view(torch.float32))
-        target = MixedTarget(d64[1], d64[3], dev[23 * B:24 * B].view(torch.float32))
-        return (args, target) if erase is None else (args, target, self._erase_views(dev, 24 * B, erase))
+            vals.update(erect=erase[0], ekey=u32_bits(erase[1]))
+        layout = _param_layout(len(kidx), mix is not None, 0 if erase is None else erase[0].shape[1])
+        host = torch.empty(sum(n for _, n, _, _ in layout.values()), dtype=torch.int32, pin_memory=True)
+        for name, view in _block_views(host, layout).items():
+            view.copy_(vals[name])
+        d = _block_views(host.to(self.device, non_blocking=True), layout)
+        target = d["labels"] if mix is None else MixedTarget(d["labels"], d["plabels"], d["lam"])
+        mixed = None if mix is None else (d["pidx"], d["pbox"], d["rect"], d["w_own"])
+        return target, (d["kidx"], d["box"], mixed, None if erase is None else (d["erect"], d["ekey"]))
 
     def _batch(self, src, kidx, labels, box, mix, erase=None):
         """Upload one batch's parameters and launch: ``(images, labels or MixedTarget)``."""
-        if erase is None:
-            if mix is None:
-                kidx_d, y, box_d = self._upload_params(kidx, labels, box)
-                return self._launch(src, kidx_d, box_d), y
-            (kidx_d, box_d, *mixed), target = self._upload_mixed(kidx, labels, box, mix)
-            return self._launch(src, kidx_d, box_d, mixed), target
-        if mix is None:
-            kidx_d, y, box_d, erased = self._upload_params(kidx, labels, box, erase)
-            return self._launch(src, kidx_d, box_d, None, erased), y
-        (kidx_d, box_d, *mixed), target, erased = self._upload_mixed(kidx, labels, box, mix, erase)
-        return self._launch(src, kidx_d, box_d, mixed, erased), target
+        target, args = self._upload(kidx, labels, box, mix, erase)
+        return self._launch(src, *args), target
 
     def _launch(self, src, kidx, box, mixed=None, erased=None):
-        from ..ops import native_ops
+        from ..ops.native_ops.data import _crop_resize_norm
         B, S = box.shape[0], self.image_size
         buf = torch.empty((B, S, S, 4), dtype=torch.bfloat16, device=self.device)
-        if erased is not None:
-            native_ops.crop_resize_normalize_erase(src, kidx, box, mixed, *erased, self.re_mode, buf, self.mean,
-                                                   self.std)
-        elif mixed is None:
-            native_ops.crop_resize_normalize(src, kidx, box, buf, self.mean, self.std)
-        else:
-            native_ops.crop_resize_normalize_mix(src, kidx, box, *mixed, buf, self.mean, self.std)
+        _crop_resize_norm(src, kidx, box, mixed, erased, self.re_mode, buf, self.mean, self.std)
         x = buf[..., :3].permute(0, 3, 1, 2)
         x.pdt_nhwc_pad = 4
         return x

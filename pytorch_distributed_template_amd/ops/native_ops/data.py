@@ -25,6 +25,50 @@ def synthetic_images_at(buf, idx, C, seed, labels, num_classes):
                                        int(num_classes), _s()), "synth_images")
 
 
+_ERASE_MODES = {"const": 0, "pixel": 1}
+
+
+def _is(t, dtype, shape, src):
+    return t is not None and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() \
+        and t.device == src.device
+
+
+def _crop_resize_norm(src, idx, box, mixed, erased, mode, out, mean, std):
+    """The checks and the call behind the three functions below: ``mixed`` None or ``(pidx, pbox,
+    rect, w_own)``, ``erased`` None or ``(erect, ekey)`` with its ``mode``."""
+    assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and src.is_contiguous()
+    assert out.dtype == torch.bfloat16 and out.dim() == 4 and out.is_contiguous() and out.device == src.device
+    B, S, S2, Cp = out.shape
+    assert S == S2 and Cp % 4 == 0 and B > 0
+    assert _is(box, torch.int32, (B, 5), src)
+    assert _is(idx, torch.int64, (B,), src) if idx is not None else src.shape[0] >= B
+    pidx = pbox = rect = w_own = None
+    if mixed is not None:
+        pidx, pbox, rect, w_own = mixed
+        assert _is(pidx, torch.int64, (B,), src) and _is(pbox, torch.int32, (B, 5), src)
+        assert _is(rect, torch.int32, (B, 4), src) and _is(w_own, torch.float32, (B,), src)
+    if erased is not None:
+        erect, ekey = erased
+        assert erect.dim() == 3 and 1 <= erect.shape[1] <= 8 and _is(erect, torch.int32, (B, erect.shape[1], 4), src)
+        assert _is(ekey, torch.int32, (B,), src)
+        assert mode in _ERASE_MODES, mode
+    assert len(mean) == 3 and len(std) == 3 and all(float(s) > 0 for s in std)
+    m = (c_float * 3)(*[float(v) for v in mean])
+    inv = (c_float * 3)(*[1.0 / float(v) for v in std])
+    n, Hs, Ws, _ = src.shape
+    head = (_p(src), Hs, Ws, _p(idx), _p(box))
+    tail = (_p(out), B, S, Cp, ctypes.addressof(m), ctypes.addressof(inv), _s())
+    if erased is not None:
+        _chk(_load().pdt_crop_resize_norm_erase_u8_bf16(*head, _p(pidx), _p(pbox), _p(rect), _p(w_own), _p(erect),
+                                                        int(erect.shape[1]), _p(ekey), _ERASE_MODES[mode], *tail),
+             "crop_resize_norm_erase")
+    elif mixed is not None:
+        _chk(_load().pdt_crop_resize_norm_mix_u8_bf16(*head, _p(pidx), _p(pbox), _p(rect), _p(w_own), *tail),
+             "crop_resize_norm_mix")
+    else:
+        _chk(_load().pdt_crop_resize_norm_u8_bf16(*head, *tail), "crop_resize_norm")
+
+
 def crop_resize_normalize(src, idx, box, out, mean, std):
     """The packed-image input pipeline in one launch (``csrc/image_aug.hip``): output ``b`` is the
     crop ``box[b] = (y0, x0, h, w, flip)`` of stored image ``idx[b]`` (``idx`` None: image ``b``),
@@ -34,22 +78,7 @@ def crop_resize_normalize(src, idx, box, out, mean, std):
     ``src`` uint8 [n, Hs, Ws, 3]; ``idx`` int64 [B] or None; ``box`` int32 [B, 5]; ``out`` bf16
     [B, S, S, Cp] (channel 3 is written as 0); all on one device. ``mean`` / ``std``: 3 floats.
     The kernel trusts the boxes and indices: validate them on the host (``data/packed.py``)."""
-    assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and src.is_contiguous()
-    assert out.dtype == torch.bfloat16 and out.dim() == 4 and out.is_contiguous() and out.device == src.device
-    B, S, S2, Cp = out.shape
-    assert S == S2 and Cp % 4 == 0 and B > 0
-    assert box.dtype == torch.int32 and tuple(box.shape) == (B, 5) and box.is_contiguous() and box.device == src.device
-    if idx is not None:
-        assert idx.dtype == torch.int64 and tuple(idx.shape) == (B,) and idx.is_contiguous() \
-            and idx.device == src.device
-    else:
-        assert src.shape[0] >= B
-    assert len(mean) == 3 and len(std) == 3 and all(float(s) > 0 for s in std)
-    m = (c_float * 3)(*[float(v) for v in mean])
-    inv = (c_float * 3)(*[1.0 / float(v) for v in std])
-    n, Hs, Ws, _ = src.shape
-    _chk(_load().pdt_crop_resize_norm_u8_bf16(_p(src), Hs, Ws, _p(idx), _p(box), _p(out), B, S, Cp,
-                                              ctypes.addressof(m), ctypes.addressof(inv), _s()), "crop_resize_norm")
+    _crop_resize_norm(src, idx, box, None, None, None, out, mean, std)
 
 
 def crop_resize_normalize_mix(src, idx, box, pidx, pbox, rect, w_own, out, mean, std):
@@ -63,34 +92,7 @@ def crop_resize_normalize_mix(src, idx, box, pidx, pbox, rect, w_own, out, mean,
     ``pidx`` int64 [B]; ``pbox`` int32 [B, 5]; ``rect`` int32 [B, 4] inside ``[0, S]^2``; ``w_own``
     float32 [B] in [0, 1]; the rest as in :func:`crop_resize_normalize`. The kernel trusts them
     all: validate on the host (``data/packed.py``: ``validate_boxes``, ``validate_mix``)."""
-    assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and src.is_contiguous()
-    assert out.dtype == torch.bfloat16 and out.dim() == 4 and out.is_contiguous() and out.device == src.device
-    B, S, S2, Cp = out.shape
-    assert S == S2 and Cp % 4 == 0 and B > 0
-    assert box.dtype == torch.int32 and tuple(box.shape) == (B, 5) and box.is_contiguous() and box.device == src.device
-    if idx is not None:
-        assert idx.dtype == torch.int64 and tuple(idx.shape) == (B,) and idx.is_contiguous() \
-            and idx.device == src.device
-    else:
-        assert src.shape[0] >= B
-    assert pidx is not None and pidx.dtype == torch.int64 and tuple(pidx.shape) == (B,) and pidx.is_contiguous() \
-        and pidx.device == src.device
-    assert pbox.dtype == torch.int32 and tuple(pbox.shape) == (B, 5) and pbox.is_contiguous() \
-        and pbox.device == src.device
-    assert rect.dtype == torch.int32 and tuple(rect.shape) == (B, 4) and rect.is_contiguous() \
-        and rect.device == src.device
-    assert w_own.dtype == torch.float32 and tuple(w_own.shape) == (B,) and w_own.is_contiguous() \
-        and w_own.device == src.device
-    assert len(mean) == 3 and len(std) == 3 and all(float(s) > 0 for s in std)
-    m = (c_float * 3)(*[float(v) for v in mean])
-    inv = (c_float * 3)(*[1.0 / float(v) for v in std])
-    n, Hs, Ws, _ = src.shape
-    _chk(_load().pdt_crop_resize_norm_mix_u8_bf16(_p(src), Hs, Ws, _p(idx), _p(box), _p(pidx), _p(pbox), _p(rect),
-                                                  _p(w_own), _p(out), B, S, Cp, ctypes.addressof(m),
-                                                  ctypes.addressof(inv), _s()), "crop_resize_norm_mix")
-
-
-_ERASE_MODES = {"const": 0, "pixel": 1}
+    _crop_resize_norm(src, idx, box, (pidx, pbox, rect, w_own), None, None, out, mean, std)
 
 
 def crop_resize_normalize_erase(src, idx, box, mixed, erect, ekey, mode, out, mean, std):
@@ -106,40 +108,7 @@ def crop_resize_normalize_erase(src, idx, box, mixed, erect, ekey, mode, out, me
     ``erect`` int32 [B, R, 4] inside ``[0, S]^2``, R in 1..8; ``ekey`` int32 [B] holding the uint32
     keys' bits; the rest as in the two functions above. The kernel trusts them all: validate on the
     host (``data/packed.py``: ``validate_erase``)."""
-    assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and src.is_contiguous()
-    assert out.dtype == torch.bfloat16 and out.dim() == 4 and out.is_contiguous() and out.device == src.device
-    B, S, S2, Cp = out.shape
-    assert S == S2 and Cp % 4 == 0 and B > 0
-    assert box.dtype == torch.int32 and tuple(box.shape) == (B, 5) and box.is_contiguous() and box.device == src.device
-    if idx is not None:
-        assert idx.dtype == torch.int64 and tuple(idx.shape) == (B,) and idx.is_contiguous() \
-            and idx.device == src.device
-    else:
-        assert src.shape[0] >= B
-    pidx = pbox = rect = w_own = None
-    if mixed is not None:
-        pidx, pbox, rect, w_own = mixed
-        assert pidx.dtype == torch.int64 and tuple(pidx.shape) == (B,) and pidx.is_contiguous() \
-            and pidx.device == src.device
-        assert pbox.dtype == torch.int32 and tuple(pbox.shape) == (B, 5) and pbox.is_contiguous() \
-            and pbox.device == src.device
-        assert rect.dtype == torch.int32 and tuple(rect.shape) == (B, 4) and rect.is_contiguous() \
-            and rect.device == src.device
-        assert w_own.dtype == torch.float32 and tuple(w_own.shape) == (B,) and w_own.is_contiguous() \
-            and w_own.device == src.device
-    assert erect.dtype == torch.int32 and erect.dim() == 3 and erect.shape[0] == B and 1 <= erect.shape[1] <= 8 \
-        and erect.shape[2] == 4 and erect.is_contiguous() and erect.device == src.device
-    assert ekey.dtype == torch.int32 and tuple(ekey.shape) == (B,) and ekey.is_contiguous() \
-        and ekey.device == src.device
-    assert mode in _ERASE_MODES, mode
-    assert len(mean) == 3 and len(std) == 3 and all(float(s) > 0 for s in std)
-    m = (c_float * 3)(*[float(v) for v in mean])
-    inv = (c_float * 3)(*[1.0 / float(v) for v in std])
-    n, Hs, Ws, _ = src.shape
-    _chk(_load().pdt_crop_resize_norm_erase_u8_bf16(_p(src), Hs, Ws, _p(idx), _p(box), _p(pidx), _p(pbox), _p(rect),
-                                                    _p(w_own), _p(erect), int(erect.shape[1]), _p(ekey),
-                                                    _ERASE_MODES[mode], _p(out), B, S, Cp, ctypes.addressof(m),
-                                                    ctypes.addressof(inv), _s()), "crop_resize_norm_erase")
+    _crop_resize_norm(src, idx, box, mixed, (erect, ekey), mode, out, mean, std)
 
 
 def synthetic_images(shape, dtype, device, seed=0, channels_last=True):
