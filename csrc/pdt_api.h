@@ -157,6 +157,11 @@ PDT_API int pdt_drop_path_scales(float* scale, int* state, const float* p, const
 PDT_API int pdt_ema_update(const void* chunks, int nchunks, void* ema, const void* src, void* shadows, float* dev,
                            float decay, int warmup, hipStream_t st);
 
+// eval_stats.hip (ks: nk <= 8 ints in HOST memory; loss_sum / counts are added to)
+PDT_API int pdt_eval_stats(const void* logits, int bf16, long ld, const long* target, int kind, float eps,
+                           const int* ks, int nk, float* loss_rows, int* rank, double* loss_sum, long* counts, int B,
+                           int V, hipStream_t st);
+
 // fp8.hip
 PDT_API int pdt_amax_blocks(long n);
 PDT_API int pdt_amax_partial(const void* x, int bf16, long n, float* partial, hipStream_t st);

@@ -173,6 +173,18 @@ __device__ __forceinline__ float warp_max(float v) {
   return row16_reduce(xor16_reduce(xor32_reduce(v, MaxOp{}), MaxOp{}), MaxOp{});
 }
 
+// the same for an integer count (exact: no float round trip)
+__device__ __forceinline__ int warp_sum_i(int v) {
+  const auto a = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
+  v = (int)(a[0] + a[1]);
+  const auto b = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+  v = (int)(b[0] + b[1]);
+  v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true);
+  v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true);
+  v += __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true);
+  return v + __builtin_amdgcn_mov_dpp(v, 0x140, 0xF, 0xF, true);
+}
+
 // Fast unsigned division by a runtime-constant divisor (Granlund-Montgomery).
 struct FastDiv {
   uint32_t d, m, s;

@@ -25,3 +25,8 @@ def cross_entropy(output, target):
 
 def label_smoothing_cross_entropy(output, target, smoothing=0.1):
     return fused.softmax_cross_entropy(output, target, label_smoothing=smoothing)
+
+
+# Registry losses that streaming validation can sum row by row (``fused.eval_stats_update``):
+# name -> (kind, label smoothing)
+EVAL_FORMS = {"cross_entropy": ("ce", 0.0), "label_smoothing_cross_entropy": ("ce", 0.1), "nll_loss": ("nll", 0.0)}

@@ -26,3 +26,13 @@ def accuracy(output, target):
 def top_k_acc(output, target, k=3):
     assert output.shape[0] == len(target)
     return topk_correct_count(output, target, k).item() / len(target)
+
+
+def top5_acc(output, target):
+    return top_k_acc(output, target, 5)
+
+
+# Registry metrics that have a count form -- "the target is among the k largest", a count of rows
+# that streaming validation (``trainer.eval_mode: "stream"``, ``trainer/streaming.py``) adds up on
+# the device instead of scoring gathered logits: name -> k
+COUNT_FORMS = {"accuracy": 1, "top_k_acc": 3, "top5_acc": 5}

@@ -304,3 +304,66 @@ def softmax_cross_entropy(logits, target, label_smoothing: float = 0.0):
         from . import native_ops
         return native_ops.softmax_cross_entropy(logits, target, label_smoothing)
     return F.cross_entropy(logits.float(), target, label_smoothing=label_smoothing)
+
+
+EVAL_MAX_K = 8  # the k values one eval_stats_update takes (csrc/eval_stats.hip)
+
+
+def eval_stats_new(ks, device):
+    """Zeroed accumulators for :func:`eval_stats_update`: ``(loss_sum float64 [1], counts int64
+    [2 + len(ks)])`` -- rows, out-of-range targets, rows correct at each ``k``."""
+    return (torch.zeros(1, dtype=torch.float64, device=device),
+            torch.zeros(2 + len(ks), dtype=torch.int64, device=device))
+
+
+def _torch_eval_rows(logits, target, kind, eps):
+    """Per-row ``(loss float64 [B], rank int64 [B])`` of csrc/eval_stats.hip's definition from
+    comparisons and sums (no ``topk``): ``rank = #{j: x[j] > x[t]} + #{j < t: x[j] == x[t]}``, the
+    target's position in a stable descending sort; ``V`` for a row with a NaN or a target outside
+    ``[0, V)``, whose loss is 0."""
+    x = logits.float() if logits.dtype != torch.float64 else logits
+    B, V = x.shape
+    t = target.to(torch.long).reshape(B)
+    valid = (t >= 0) & (t < V)
+    tc = t.clamp(0, V - 1).unsqueeze(1)
+    xt = x.gather(1, tc)
+    cols = torch.arange(V, device=x.device).unsqueeze(0)
+    above = (x > xt).sum(1) + ((x == xt) & (cols < tc)).sum(1)
+    rank = torch.where(valid & ~torch.isnan(x).any(1), above, torch.full_like(above, V))
+    x64 = x.double()
+    if kind == "nll":
+        rows = -x64.gather(1, tc)[:, 0]
+    else:
+        rows = torch.logsumexp(x64, 1) - (1.0 - eps) * x64.gather(1, tc)[:, 0] - eps * x64.mean(1)
+    return torch.where(valid, rows, torch.zeros_like(rows)), rank
+
+
+def eval_stats_update(logits, target, loss_sum, counts, ks, kind: str = "ce", eps: float = 0.0):
+    """Score one batch and ADD it into the accumulators of :func:`eval_stats_new` -- streaming
+    validation: no logits kept, no host sync. ``logits`` [B, V]; ``target`` int64 [B]; ``kind``
+    ``"ce"`` (cross-entropy with label smoothing ``eps``) or ``"nll"`` (``-x[t]`` on
+    log-probabilities); ``ks``: up to 8 values ``k >= 1``. A row is correct at ``k`` iff its target's
+    rank (see ``_torch_eval_rows``) is below ``min(k, V)``; rank 0 is exactly ``torch.argmax == t``.
+    Native: one pass over the logits and a one-workgroup reduce (``pdt_eval_stats``); torch path:
+    the same definition, the loss summed in float64. Returns the per-row ``(loss, rank)``."""
+    ks = tuple(int(k) for k in ks)
+    if kind not in ("ce", "nll"):
+        raise ValueError(f'eval_stats_update: kind must be "ce" or "nll", got {kind!r}')
+    if len(ks) > EVAL_MAX_K or any(k < 1 for k in ks):
+        raise ValueError(f"eval_stats_update: at most {EVAL_MAX_K} values k >= 1, got {ks}")
+    if logits.dim() != 2 or target.numel() != logits.shape[0]:
+        raise ValueError(f"eval_stats_update: logits {tuple(logits.shape)} / target {tuple(target.shape)} "
+                         "(expected [B, V] and [B])")
+    if logits.shape[0] == 0:
+        return logits.new_zeros(0, dtype=torch.float32), target.new_zeros(0, dtype=torch.int32)
+    if _use_native(logits):
+        from . import native_ops
+        return native_ops.eval_stats(logits, target, ks, loss_sum, counts, kind=kind, eps=eps)
+    with torch.no_grad():
+        rows, rank = _torch_eval_rows(logits, target, kind, float(eps))
+        V = logits.shape[1]
+        loss_sum += rows.sum()
+        new = [torch.tensor(rows.numel(), device=rank.device), ((target < 0) | (target >= V)).sum()]
+        new += [(rank < min(k, V)).sum() for k in ks]
+        counts += torch.stack(new)
+    return rows, rank

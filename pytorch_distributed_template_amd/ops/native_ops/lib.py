@@ -29,7 +29,7 @@ c_int, c_long, c_float, c_double, c_void_p, c_uint = (ctypes.c_int, ctypes.c_lon
 _API_HEADER = CSRC / "pdt_api.h"
 _SCALARS = {"int": c_int, "long": c_long, "unsigned": c_uint, "float": c_float, "double": c_double,
             "hipStream_t": c_void_p}
-_POINTEES = ("void", "float", "int", "long", "int64_t")
+_POINTEES = ("void", "float", "double", "int", "long", "int64_t")
 _DECL = re.compile(r"^PDT_API\s+([^;()]*?)(\w+)\s*\(([^;()]*)\)\s*;", re.M)
 
 

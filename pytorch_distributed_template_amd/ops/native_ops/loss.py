@@ -1,11 +1,12 @@
-"""softmax cross-entropy, and the NLL loss with its lazy target check"""
+"""softmax cross-entropy, the streaming evaluation statistics, and the NLL loss with its lazy target check"""
 from __future__ import annotations
 
+import ctypes
 import os
 
 import torch
 
-from .lib import _chk, _load, _p, _s, fallback
+from .lib import _chk, _load, _p, _s, c_int, fallback
 from .tuning import _capturing
 
 
@@ -88,6 +89,52 @@ def softmax_cross_entropy(logits, target, label_smoothing=0.0):
         fallback("softmax_cross_entropy", f"logits of shape {tuple(logits.shape)} (kernel: [B, V])")
         return torch.nn.functional.cross_entropy(logits.float(), target, label_smoothing=label_smoothing)
     return _XEnt.apply(logits, target, float(label_smoothing))
+
+
+EVAL_KINDS = {"ce": 0, "nll": 1}  # pdt_eval_stats' loss kinds
+_EVAL_KS = {}  # (k, ...) -> the host int array the entry point reads (kept alive: built once per tuple)
+
+
+def eval_stats(logits, target, ks, loss_sum, counts, kind="ce", eps=0.0, loss_rows=None, rank=None):
+    """``pdt_eval_stats``: score the rows of ``logits`` [B, V] (bf16 or fp32, last dimension dense,
+    any row stride) against ``target`` [B] and ADD the batch into ``loss_sum`` (float64 [1]) and
+    ``counts`` (int64 [2 + len(ks)]: rows, out-of-range targets, rows with rank < k for each k).
+    Two launches, no host sync. Returns the per-row ``(loss_rows fp32 [B], rank int32 [B])`` (given,
+    or allocated here)."""
+    if logits.dim() != 2:
+        raise ValueError(f"eval_stats: logits of shape {tuple(logits.shape)} (kernel: [B, V])")
+    if logits.dtype not in (torch.bfloat16, torch.float32):
+        logits = logits.float()
+    B, V = logits.shape
+    if V > 1 and logits.stride(1) != 1:
+        logits = logits.contiguous()
+    ld = logits.stride(0) if B > 1 else V
+    if ld < V:  # (an expanded or overlapping view)
+        logits, ld = logits.contiguous(), V
+    dev = logits.device
+    target = target.to(torch.long).contiguous()
+    ks = tuple(int(k) for k in ks)
+    if target.numel() != B or target.device != dev:
+        raise ValueError(f"eval_stats: target {tuple(target.shape)} on {target.device} for logits "
+                         f"{tuple(logits.shape)} on {dev}")
+    if loss_sum.dtype != torch.float64 or loss_sum.numel() != 1 or counts.dtype != torch.int64 \
+            or counts.numel() != 2 + len(ks) or not counts.is_contiguous() or loss_sum.device != dev \
+            or counts.device != dev:
+        raise ValueError("eval_stats: loss_sum must be float64 [1] and counts contiguous int64 [2 + len(ks)] on "
+                         "the logits' device")
+    if loss_rows is None:
+        loss_rows = torch.empty(B, dtype=torch.float32, device=dev)
+    if rank is None:
+        rank = torch.empty(B, dtype=torch.int32, device=dev)
+    assert loss_rows.dtype == torch.float32 and rank.dtype == torch.int32
+    assert loss_rows.numel() == B and rank.numel() == B and loss_rows.is_contiguous() and rank.is_contiguous()
+    host_ks = _EVAL_KS.get(ks)
+    if host_ks is None:
+        host_ks = _EVAL_KS[ks] = (c_int * max(len(ks), 1))(*ks)
+    _chk(_load().pdt_eval_stats(_p(logits), int(logits.dtype == torch.bfloat16), ld, _p(target), EVAL_KINDS[kind],
+                                float(eps), ctypes.addressof(host_ks), len(ks), _p(loss_rows), _p(rank),
+                                _p(loss_sum), _p(counts), B, V, _s()), "eval_stats")
+    return loss_rows, rank
 
 
 class _TargetCheck:

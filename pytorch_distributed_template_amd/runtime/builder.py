@@ -21,7 +21,8 @@ Extra (optional) ``trainer`` keys, all defaulting to reference behaviour:
   ema {decay, warmup, validate "both"|"ema"|"model"} (``optim.ModelEMA``, updated after every
   optimizer step; absent / null: off), lr_step "epoch"|"iteration" (when the scheduler steps),
   log_grad_norm bool (``grad_norm`` / ``skipped_steps`` of an ``optim.Fused*`` optimizer in the
-  epoch log).
+  epoch log), eval_mode "gather"|"stream" (``trainer/streaming.py``: validation scored batch by
+  batch on the device instead of on logits gathered to rank 0).
 """
 from __future__ import annotations
 

@@ -42,7 +42,13 @@ MI355X-first changes to the hot loop:
     ``skip_nonfinite`` declined in the epoch);
   * ``trainer.lr_step``: ``"epoch"`` (default, the reference's) or ``"iteration"`` -- the
     scheduler steps after every optimizer step, graph replays included (the host value; a
-    capturable optimizer's ``refresh_scalars()`` carries it to the device before each replay).
+    capturable optimizer's ``refresh_scalars()`` carries it to the device before each replay);
+  * ``trainer.eval_mode``: ``"gather"`` (default: the validation described above) or ``"stream"``
+    (``trainer/streaming.py``): every batch's logits are scored on the device in one pass
+    (``csrc/eval_stats.hip``) that adds the loss sum and the top-k correct counts into a few device
+    scalars; a validation pass ends with one small all-reduce, keeps no logits, gathers nothing
+    and never waits for a batch. Needs a loss and metrics with a row-wise form
+    (``models.loss.EVAL_FORMS``, ``models.metric.COUNT_FORMS``); the log keys are the same.
 """
 from __future__ import annotations
 
@@ -55,6 +61,7 @@ from ..base.base_trainer import BaseTrainer
 from ..utils import MetricTracker, inf_loop
 from ..utils import dist as pdist
 from ..utils.profiling import PhaseTimer
+from .streaming import StreamingEval, eval_mode
 
 
 GRAPH_WARMUP = 11  # eager steps before the capture (DDP's runtime statistics cover iterations 1..10)
@@ -150,6 +157,13 @@ class Trainer(BaseTrainer):
             self.ema_validate = getattr(self.ema, "validate", "both")  # (checked by runtime.build_ema)
             self.valid_ema_metrics = MetricTracker("ema_loss", *["ema_" + m.__name__ for m in self.metric_ftns],
                                                    writer=self.writer)
+        # "gather": logits of the whole set to rank 0; "stream": device accumulators (one per tracker)
+        self.eval_mode = eval_mode(config)
+        self._stream_evals = {}
+        if self.eval_mode == "stream":
+            self._stream_evals[""] = StreamingEval(criterion, self.metric_ftns, device)
+            if self.ema is not None:
+                self._stream_evals["ema_"] = StreamingEval(criterion, self.metric_ftns, device)
         self.lr_step = config["trainer"].get("lr_step", "epoch")
         if self.lr_step not in ("epoch", "iteration"):
             raise ValueError(f'trainer.lr_step must be "epoch" or "iteration", got {self.lr_step!r}')
@@ -396,6 +410,23 @@ class Trainer(BaseTrainer):
             self._replayed[who] = False
         model.eval()
         tracker.reset()
+        if self.eval_mode == "stream":
+            acc = self._stream_evals[prefix]
+            acc.reset()
+            for data, target in self.valid_data_loader:
+                data, target = self._to_device(data, target)
+                with self._autocast():
+                    output = model(data)
+                acc.update(output, target)
+            scores = acc.result(prefix)  # (one all-reduce: every rank)
+            result = {}
+            if pdist.is_main_process():
+                for key, value in scores.items():
+                    tracker.update(key, value)
+                result = tracker.result()
+            if model is self.model:
+                model.train()
+            return result
         outputs, targets = [], []
         loss_sum = torch.zeros((), dtype=torch.float64, device=self.device)
         n = 0

@@ -10,6 +10,8 @@ only tensors and plain dicts), runs distributed inference over
 ``test_loader`` with unpadded per-rank shards, gathers logits/targets to
 rank 0 as fixed-shape tensors and logs
 ``{'loss': sum(loss*bs)/len(dataset), <metric>: ...}`` like the reference.
+With ``trainer.eval_mode: "stream"`` the loss sum and the top-k counts are added up on the device
+batch by batch instead (``trainer/streaming.py``): no logits are kept and nothing is gathered.
 Fixes ``--seed`` (the reference hit a NameError).
 """
 import argparse
@@ -20,6 +22,7 @@ from pytorch_distributed_template_amd.base.base_trainer import load_checkpoint, 
 from pytorch_distributed_template_amd.config import ConfigParser
 from pytorch_distributed_template_amd.runtime import (autocast_dtype, build_criterion_metrics, build_loader,
                                                       build_model)
+from pytorch_distributed_template_amd.trainer.streaming import StreamingEval, eval_mode
 from pytorch_distributed_template_amd.utils import dist as pdist
 from pytorch_distributed_template_amd.utils.util import seed_everything, set_deterministic
 
@@ -45,6 +48,7 @@ def main(args, config, device):
 
     ac = autocast_dtype(config, device)
     channels_last = config["trainer"].get("channels_last", False)
+    stream = StreamingEval(loss_fn, metric_fns, device) if eval_mode(config) == "stream" else None
     total_loss = torch.zeros((), dtype=torch.float64, device=device)
     outputs, targets = [], []
     for data, target in data_loader:
@@ -55,11 +59,19 @@ def main(args, config, device):
             data = data.contiguous(memory_format=torch.channels_last)
         with torch.autocast(device_type=device.type, dtype=ac or torch.float32, enabled=ac is not None):
             output = model(data)
+            if stream is not None:  # scored on the device: no logits kept, nothing gathered
+                stream.update(output, target)
+                continue
             loss = loss_fn(output, target)
         outputs.append(output.float())
         targets.append(target)
         total_loss += loss.double() * data.shape[0]
 
+    if stream is not None:
+        log = stream.result()  # one all-reduce; the same on every rank
+        if pdist.is_main_process():
+            logger.info(log)
+        return log
     out = torch.cat(outputs) if outputs else torch.zeros((0, 1), device=device)
     tgt = torch.cat(targets) if targets else torch.zeros((0,), dtype=torch.long, device=device)
     if pdist.get_world_size() > 1:
