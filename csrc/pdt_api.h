@@ -244,6 +244,17 @@ PDT_API int pdt_ln_dp_bwd(const void* dy, const void* x, const float* g, const f
                           hipStream_t st);
 PDT_API int pdt_gelu_bwd(const void* dy, const void* z, void* dz, long n, hipStream_t st);
 
+// layernorm_rows.hip
+PDT_API int pdt_lnr_fwd(const void* x, const float* g, const float* b, void* y, float* mean, float* rstd, int rows,
+                        int D, float eps, hipStream_t st);
+PDT_API int pdt_lnr_add_fwd(const void* x, const void* r, void* xsum, const float* g, const float* b, void* y,
+                            float* mean, float* rstd, int rows, int D, float eps, const float* scale,
+                            int rows_per_sample, hipStream_t st);
+PDT_API int pdt_lnr_bwd_blocks(int rows, int D);
+PDT_API int pdt_lnr_bwd(const void* dy, const void* x, const float* g, const float* mean, const float* rstd, void* dx,
+                        void* dyb, float* dg, float* db, float* part, int rows, int D, int accumulate,
+                        const void* addend, const float* scale, int rows_per_sample, hipStream_t st);
+
 // lenet.hip
 PDT_API int pdt_lenet_grad_row(int nc);
 PDT_API int pdt_lenet_fwd(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,

@@ -270,3 +270,17 @@ def vit_b_16(num_classes=1000, **kw):
 class ViT_B_16(VisionTransformer):
     def __init__(self, num_classes=1000, fp8=False, **kw):
         super().__init__(num_classes=num_classes, fp8=fp8, **kw)
+
+
+class ViT_S_16(VisionTransformer):
+    """DeiT-S: d=384, 6 heads (head dim 64), depth 12. LayerNorm on csrc/layernorm_rows.hip."""
+
+    def __init__(self, num_classes=1000, fp8=False, **kw):
+        super().__init__(num_classes=num_classes, fp8=fp8, embed_dim=384, num_heads=6, **kw)
+
+
+class ViT_Ti_16(VisionTransformer):
+    """DeiT-Ti: d=192, 3 heads (head dim 64), depth 12. LayerNorm on csrc/layernorm_rows.hip."""
+
+    def __init__(self, num_classes=1000, fp8=False, **kw):
+        super().__init__(num_classes=num_classes, fp8=fp8, embed_dim=192, num_heads=3, **kw)

@@ -25,13 +25,16 @@ ARCH = os.environ.get("PDT_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-Wno-unused-result"]
+# per-source flags. layernorm_rows.hip: no packed-fp32 instruction selection -- its sums and
+# products are written out one rounding at a time and are meant to be issued that way
+EXTRA_FLAGS = {"layernorm_rows.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _compile(src: Path, headers_mtime: float) -> Path:
     obj = OBJ_DIR / (src.stem + ".o")
     if obj.exists() and obj.stat().st_mtime >= max(src.stat().st_mtime, headers_mtime):
         return obj
-    cmd = [HIPCC, *FLAGS, "-I", str(CSRC), "-c", str(src), "-o", str(obj)]
+    cmd = [HIPCC, *FLAGS, *EXTRA_FLAGS.get(src.name, []), "-I", str(CSRC), "-c", str(src), "-o", str(obj)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"hipcc failed for {src.name}:\n{r.stdout}\n{r.stderr}")

@@ -42,8 +42,78 @@ class _LayerNorm(torch.autograd.Function):
         return dx.reshape(ctx.shp), dg, db, None
 
 
+def _rows_width(D) -> bool:
+    """Widths of csrc/layernorm_rows.hip: every D % 8 == 0 up to 1016 that is no multiple of 256
+    (those keep csrc/layernorm.hip's kernels)."""
+    return D % 8 == 0 and 8 <= D <= 1016 and D % 256 != 0
+
+
+class _LNRows(torch.autograd.Function):
+    """(s, LayerNorm(s)) on csrc/layernorm_rows.hip, bf16 only: s = x (``r`` None: _LNFork), s =
+    x + r (_LNAddFork) or s = r + scale[b] * x (``scale``: _LNAddDropFork), with the same
+    gradients. These widths have no fp8 flavours: the LayerNorm emits no codes, and the fp8 linear
+    layers around it cast their own inputs and gradients and form their own bias gradients."""
+
+    @staticmethod
+    def forward(ctx, x, r, g, b, eps, scale, rps):
+        ctx.refs = (g, b)
+        shp = x.shape
+        D = shp[-1]
+        x2 = x.reshape(-1, D).contiguous()
+        rows = x2.shape[0]
+        h = torch.empty_like(x2)
+        stats = torch.empty((2, rows), dtype=torch.float32, device=x.device)
+        gf, bf = g.float().contiguous(), b.float().contiguous()
+        lib = _load()
+        saved = ()
+        if r is None:
+            xs = x2
+            _chk(lib.pdt_lnr_fwd(_p(x2), _p(gf), _p(bf), _p(h), _p(stats[0]), _p(stats[1]), rows, D, float(eps),
+                                 _s()), "lnr_fwd")
+        else:
+            r2 = r.reshape(-1, D).to(torch.bfloat16).contiguous()
+            xs = torch.empty_like(x2)
+            sc = None
+            if scale is not None:
+                sc = scale.detach().float().contiguous()
+                assert sc.numel() * rps == rows and sc.device == x.device, (tuple(sc.shape), rps, rows)
+                saved = (sc,)
+            _chk(lib.pdt_lnr_add_fwd(_p(x2), _p(r2), _p(xs), _p(gf), _p(bf), _p(h), _p(stats[0]), _p(stats[1]), rows,
+                                     D, float(eps), _p(sc), rps, _s()), "lnr_add_fwd")
+        ctx.save_for_backward(xs, gf, stats, *saved)
+        ctx.shp, ctx.rps, ctx.has_r = shp, rps, r is not None
+        return (x.view_as(x) if r is None else xs.reshape(shp)), h.reshape(shp)
+
+    @staticmethod
+    def backward(ctx, g_res, dy):
+        xs, gf, stats, *saved = ctx.saved_tensors
+        sc = saved[0] if saved else None
+        none = (None,) * 5
+        if dy is None:  # the normalised output fed nothing: only the add's gradients
+            gx = g_res
+            if sc is not None:
+                s = sc.repeat_interleave(ctx.rps).reshape(*ctx.shp[:-1], 1)
+                gx = torch.where(s != 0, g_res.float() * s, torch.zeros((), device=s.device)).to(g_res.dtype)
+            return (gx, g_res if ctx.has_r else None) + none
+        rows, D = xs.shape
+        lib = _load()
+        dy2 = dy.reshape(rows, D).to(torch.bfloat16).contiguous()
+        add = g_res.reshape(rows, D).to(torch.bfloat16).contiguous() if g_res is not None else None
+        dx = torch.empty_like(xs)
+        dyb = torch.empty_like(xs) if sc is not None else None
+        blocks = lib.pdt_lnr_bwd_blocks(rows, D)
+        part = torch.empty(2 * blocks * D, dtype=torch.float32, device=xs.device)
+        dg, db = _grad_buf(ctx.refs[0], (D,)), _grad_buf(ctx.refs[1], (D,))
+        _chk(lib.pdt_lnr_bwd(_p(dy2), _p(xs), _p(gf), _p(stats[0]), _p(stats[1]), _p(dx), _p(dyb), _p(dg), _p(db),
+                             _p(part), rows, D, 0, _p(add), _p(sc), ctx.rps, _s()), "lnr_bwd")
+        dx = dx.reshape(ctx.shp)
+        return (dx if sc is None else dyb.reshape(ctx.shp), dx if ctx.has_r else None, dg, db, None, None, None)
+
+
 def layer_norm(x, ln):
     D = ln.normalized_shape[-1]
+    if len(ln.normalized_shape) == 1 and _rows_width(D) and ln.elementwise_affine:
+        return _LNRows.apply(x.to(torch.bfloat16), None, ln.weight, ln.bias, ln.eps, None, 1)[1]
     if len(ln.normalized_shape) != 1 or D not in (256, 512, 768, 1024) or not ln.elementwise_affine:
         fallback("layer_norm", f"normalized_shape {tuple(ln.normalized_shape)} (kernels: D in 256/512/768/1024, affine)")
         return ln(x)
@@ -275,6 +345,15 @@ def ln_add_fork(y, r, ln, fp8_for=None, grad_fp8_for=None, scale=None, rows_per_
     1/keep) with ``rows_per_sample``: stochastic depth, the sum is r + scale[sample] * y, formed
     by the kernel's drop-path instantiation (see _LNAddDropFork)."""
     D = ln.normalized_shape[-1]
+    if (len(ln.normalized_shape) == 1 and _rows_width(D) and ln.elementwise_affine and y.dtype == torch.bfloat16
+            and r.shape == y.shape):  # no fp8 flavours at these widths (_LNRows)
+        rps = 1
+        if scale is not None:
+            rows = y.numel() // D
+            rps = rows // scale.numel() if rows_per_sample is None else int(rows_per_sample)
+            if scale.numel() * rps != rows:
+                raise ValueError(f"ln_add_fork: {scale.numel()} scales x {rps} rows per sample != {rows} rows")
+        return _LNRows.apply(y, r, ln.weight, ln.bias, ln.eps, scale, rps)
     if (len(ln.normalized_shape) != 1 or D not in (256, 512, 768, 1024) or not ln.elementwise_affine
             or y.dtype != torch.bfloat16 or r.shape != y.shape):
         if scale is not None:
@@ -316,6 +395,8 @@ def ln_fork(x, ln, fp8_for=None, grad_fp8_for=None):
     gradient is this fork's input gradient (the residual-stream producer): the LayerNorm
     backward then also writes that layer's e5m2 gradient codes (``_pdt_f8g``)."""
     D = ln.normalized_shape[-1]
+    if len(ln.normalized_shape) == 1 and _rows_width(D) and ln.elementwise_affine and x.dtype == torch.bfloat16:
+        return _LNRows.apply(x, None, ln.weight, ln.bias, ln.eps, None, 1)  # no fp8 flavours at these widths
     if (len(ln.normalized_shape) != 1 or D not in (256, 512, 768, 1024) or not ln.elementwise_affine
             or x.dtype != torch.bfloat16):
         return x, layer_norm(x, ln)
